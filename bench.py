@@ -2,7 +2,7 @@
 """Benchmark of the hot path: images/sec of one full discriminator + generator training step
 (/root/reference/model_wrapper.py:131-190 semantics incl. both Adam steps) on synthetic 256x256 batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: the script starts its own N ranks (one process per GPU, spawned BEFORE the parent touches the GPU; the parent only
 relays rank 0's JSON line) unless it already runs under ``python -m torch.distributed.run`` (RANK / WORLD_SIZE set), in which
@@ -13,6 +13,8 @@ synthetic images / labels / masks with the reference's input contract, random-in
 VGG-16, Adam lr 1e-5.  The LAST stdout line of rank 0 is ONE compact JSON record (compact_line(): < 4 KB, tests/test_bench_line.py);
 the full record (per-route tables, families, notes, parity sub-objects) goes to bench_detail.json beside this script and to stderr.
 `value` is the K timed steps of the contract, taken right after the >= 6 s `sustained` window on the same job (clocks settled).
+--dump-outputs DIR: after the K steps, one more step of the same path from the seeded start writes what it returned (dump_outputs()),
+so that runs and builds can be compared output for output on identical inputs.
 Beside the headline the full record carries (N = 1 only):
   roofline            achieved / frac: the dominant kernel; conv_frac: FLOP-weighted over every convolution launch (families: forward /
                       input gradient / weight gradient, event-timed on the launch stream in eager steps); sn3x3_bwd: the north-star's
@@ -24,6 +26,7 @@ Beside the headline the full record carries (N = 1 only):
   cpu_baseline        the CPU oracle (torch fp32 on the host cores) at batch 2 and batch 20, with the CPU model
 """
 import argparse
+import copy
 import gc
 import json
 import re
@@ -45,6 +48,8 @@ TORCH_DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16, "f32": torch.float
 DOMINANT_KERNEL = "conv3x3_pp_kernel<bf16,2> (sp_conv2d_igemm, 3x3, Cout>64, 128 co x 8x32 px tiles, ping-pong schedule)"
 DOMINANT_KERNEL_SYMBOL = r"conv3x3_pp_kernel<bf16, 2, [^>]*, 2(, false)?(, (false|true))?>\("      # regex: every epilogue form on 32-wide tiles (not the 16-wide form; optional trailing arguments: round 4's fused-tail flag - off - and round 5's window-position flag)
 TRAFFIC_FILES = ("round6_hbm_traffic_per_kernel.json", "round5_hbm_traffic_per_kernel.json", "round4_hbm_traffic_per_kernel.json", "round3_hbm_traffic_per_kernel.json", "round2_hbm_traffic_per_kernel.json")
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 4 << 20                   # elements kept of an output that would push the dump over DUMP_LIMIT_BYTES (fixed, seeded)
 
 
 def parse():
@@ -71,7 +76,14 @@ def parse():
     p.add_argument("--no-graphs", action="store_true",
                    help="launch every kernel eagerly; default: the D phase and the G phase are replayed as captured HIP "
                         "graphs (ModelWrapper.capture_graphs), which keeps a slow host from becoming the bottleneck")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, run one more step of the timed path from the seeded start (Job.step_from_start) "
+                        "and write what it returned (the five loss scalars and the generated images) as DIR/<name>.npy in float32 "
+                        "(rank 0): the same inputs on every run, whatever ran before")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -458,7 +470,7 @@ def roofline_fields(probe, peak, ips_per_gpu, batch, cf):
 # one job = (channel factor, batch, dtype) on this rank
 # ------------------------------------------------------------------------------------------------------------------
 class Job:
-    def __init__(self, cf, batch, dtype_name, dev, world, rank, use_graphs=True, device_masks=False):
+    def __init__(self, cf, batch, dtype_name, dev, world, rank, use_graphs=True, device_masks=False, keep_start=False):
         import semantic_pyramid_for_image_generation_amd as sp
         from semantic_pyramid_for_image_generation_amd import distributed, ops, params, synthetic
         self.batch, self.world = batch, world
@@ -484,6 +496,14 @@ class Job:
         images, labels, masks = images.to(dev), labels.to(dev), [m.to(dev) for m in masks]
         torch.manual_seed(100 + rank)                            # per-rank latent stream
         mask_gen = torch.Generator().manual_seed(7 + rank) if device_masks else None     # CPU generator: one host draw per batch, no device sync
+        self.start = None
+        if keep_start:
+            # the seeded start, for step_from_start(): everything a step reads and writes that carries over to the next step
+            sc = ops.loss_scaler(dev)                            # (fp16 mode: the dynamic loss scale, created here instead of lazily)
+            self.start = {"nets": [(net, {k: v.detach().clone() for k, v in net.state_dict().items()}) for net in (G, D)],
+                          "opts": [(opt, copy.deepcopy(opt.state_dict())) for opt in (opt_g, opt_d)],
+                          "scale": (sc, sc.state.clone()) if sc is not None else None,
+                          "rng": (dev, torch.cuda.get_rng_state(dev)), "mask_gen": (mask_gen, mask_gen.get_state()) if mask_gen else None}
 
         def fresh_masks():
             return synthetic.training_masks_device(batch, dev, mask_gen) if device_masks else masks
@@ -548,6 +568,27 @@ class Job:
             elapsed = float(t)
         return elapsed, {k: float(v) for k, v in out.items() if k.startswith("loss")}
 
+    def step_from_start(self):
+        """One more step of the timed path (graph replay or eager, as timed) from the seeded start kept by keep_start: parameters,
+        spectral-norm vectors, Adam moments and step counts, loss scale and random streams as before the first step, the same resident
+        batch.  What it returns depends on those inputs alone - not on how many steps ran before, whose fp32 atomics (16-bit modes)
+        add in a different order from run to run."""
+        s = self.start
+        with torch.no_grad():
+            for net, saved in s["nets"]:
+                for k, v in net.state_dict().items():
+                    v.copy_(saved[k])                            # in place: the captured graphs keep their addresses
+        for opt, saved in s["opts"]:
+            opt.load_state_dict(saved)                           # no moments yet: re-created at zero by the next step
+        if s["scale"] is not None:
+            s["scale"][0].state.copy_(s["scale"][1])
+        torch.cuda.set_rng_state(s["rng"][1], s["rng"][0])
+        if s["mask_gen"] is not None:
+            s["mask_gen"][0].set_state(s["mask_gen"][1])
+        out = self.step()
+        torch.cuda.synchronize()
+        return out
+
     def comm_stats(self, steps=5):
         """N > 1: a few extra steps with events around every collective (side stream) and every join (main stream):
         all-reduce time of the D and the G gradients and the part of it the main stream actually waited for."""
@@ -564,9 +605,25 @@ class Job:
         return st
 
     def close(self):
-        self.mw = self.step = self.eager_step = None
+        self.mw = self.step = self.eager_step = self.start = None
         gc.collect()
         torch.cuda.empty_cache()
+
+
+def dump_outputs(out, path):
+    """What one training step returned -> path/<name>.npy in float32.  An output that would take the dump over DUMP_LIMIT_BYTES is
+    written as DUMP_SAMPLE of its elements, flattened, at positions drawn from a fixed seed (ascending)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        for k, a in arrays.items():
+            if a.size > DUMP_SAMPLE:
+                idx = torch.randperm(a.size, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.numpy()
+                arrays[k] = a.reshape(-1)[idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def sub_record(cf, batch, dtype_name, dev, steps, warmup, use_graphs, probe=False):
@@ -950,7 +1007,7 @@ def main():
     if args.deterministic:
         from semantic_pyramid_for_image_generation_amd import ops as _ops1
         _ops1.set_tuning(_ops1.TUNE_DETERMINISTIC, 1)
-    job = Job(cf, args.batch, args.dtype, dev, world, rank, not args.no_graphs, args.device_masks)
+    job = Job(cf, args.batch, args.dtype, dev, world, rank, not args.no_graphs, args.device_masks, keep_start=bool(args.dump_outputs))
     # N = 1: the >= 6 s window first (power / clock steady state, sampled from sysfs while it runs), then - on the same job, with no
     # idle gap in between - the contract's W warm-up + K timed steps, which are the headline
     sustained = None
@@ -963,6 +1020,12 @@ def main():
         sustained = {"value": round(args.batch * n_sus / t_sus, 2), "unit": "images/sec", "ms_per_step": round(t_sus / n_sus * 1e3, 3),
                      "steps": n_sus, "note": ">= 6 s of back-to-back steps (power / clock steady state) right before the headline's K steps"}
     elapsed, losses = job.timed(args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs:
+        out = job.step_from_start()                  # every rank: with world > 1 the step contains collectives
+        if rank == 0:
+            dumped = dump_outputs(out, args.dump_outputs)
+        del out
     # the probe runs extra training steps: with world > 1 they contain collectives, so EVERY rank takes them
     probe = None
     probe_error = None
@@ -1012,6 +1075,8 @@ def main():
         }
         if sustained is not None:
             line["sustained"] = sustained
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "shapes": dumped, "dtype": "float32"}
         if probe_error is not None:
             line["roofline"]["probe_rejected"] = probe_error
         if world > 1:

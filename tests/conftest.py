@@ -18,7 +18,7 @@ TWO_RANK_JOB = {"proc": None, "out": None}
 
 def _wants_two_rank_job(config) -> bool:
     expr = config.getoption("-m", default="") or ""
-    if "gpu" not in expr or "not gpu" in expr:
+    if "not gpu" in expr or (expr and "gpu" not in expr):       # no -m at all: the whole suite, GPU tests included
         return False
     if config.getoption("-k", default=""):
         return "two_rank" in config.getoption("-k")

@@ -61,6 +61,16 @@ def check_checksums(state, expected, rtol=1e-6, what="", noise_keys=(), noise_at
         assert abs(s - es) <= rtol * max(1.0, abs(en), abs(es)) + 4 * noise_atol * v.numel() ** 0.5, (what, "sum", k, s, es)
 
 
+def pixel_tolerance(it, bit_exact_start):
+    """Bound on the CPU oracle's generator pixels against the reference goldens at iteration ``it`` of the loop, relative to the
+    largest reference pixel.  Iteration 0: 1e-4.  After the first Adam step the pixels also carry the sign of every gradient entry that
+    is rounding noise (Adam's first step is +-lr per element; the spectral-norm layers turn such entries into a change of the whole
+    layer's scale), so the pixels of iteration 1 depend on the host's fp32 rounding: a host that reproduces iteration 0 bit for bit
+    (``bit_exact_start``) meets 1e-4 again, one whose CPU kernels round differently was measured up to 4.4e-4 away (AMD EPYC 9575F,
+    step_cf4_b4_seed1; 3e-6 at iteration 0) and is held to 1e-3."""
+    return 1e-4 if it == 0 or bit_exact_start else 1e-3
+
+
 def zero_gradient_keys(meta, arr, key):
     """Parameters whose recorded reference gradient norm is rounding noise in every iteration."""
     norms = arr[key + "_norms"]

@@ -6,6 +6,8 @@ import os
 import sys
 from contextlib import redirect_stderr, redirect_stdout
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -70,6 +72,32 @@ def test_multi_gpu_line_is_small():
     line = bench.compact_line(d)
     assert len(json.dumps(line)) < bench.COMPACT_LIMIT
     assert line["multi_gpu"]["per_rank"] == [1301.25] * 8 and line["config"]["collectives"] == "nccl"
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    out = {"loss_generator": torch.tensor(0.25), "images_fake": torch.randn(2, 3, 8, 8, generator=torch.Generator().manual_seed(3)).bfloat16()}
+    assert bench.dump_outputs(out, str(tmp_path / "full")) == {"loss_generator": [], "images_fake": [2, 3, 8, 8]}
+    imgs = np.load(str(tmp_path / "full" / "images_fake.npy"))
+    assert imgs.dtype == np.float32 and (imgs == out["images_fake"].float().numpy()).all()
+    assert np.load(str(tmp_path / "full" / "loss_generator.npy")) == np.float32(0.25)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 256)                    # the images alone exceed it: a fixed sample of them
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 50)
+    for d in ("a", "b"):
+        assert bench.dump_outputs(out, str(tmp_path / d))["images_fake"] == [50]
+    a, b = (np.load(str(tmp_path / d / "images_fake.npy")) for d in ("a", "b"))
+    assert (a == b).all() and np.isin(a, imgs.reshape(-1)).all()
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) < 1024
+
+
+def test_parse_steps_and_dump_dir(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert (args.steps, args.warmup, args.dump_outputs) == (7, 2, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with redirect_stderr(io.StringIO()), pytest.raises(SystemExit):
+        bench.parse()
 
 
 def test_dpm_level_parsing():

@@ -16,7 +16,7 @@ def _record(timeout_s=900.0):
     from conftest import TWO_RANK_JOB
     proc, out = TWO_RANK_JOB["proc"], TWO_RANK_JOB["out"]
     if proc is None:
-        pytest.skip("the two-rank job was not started (session not selected with -m gpu, or no GPU)")
+        pytest.skip("the two-rank job was not started (GPU tests deselected, or no GPU)")
     t0 = time.time()
     while proc.poll() is None and time.time() - t0 < timeout_s:
         time.sleep(1.0)

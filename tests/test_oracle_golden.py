@@ -36,6 +36,7 @@ def test_train_step_matches_reference_loop(tag):
     pix_idx = gu.fixed_indices(batches[0][0].numel(), gu.N_PIX, 0)
     names = ("loss_discriminator_real", "loss_discriminator_fake", "loss_generator",
              "loss_generator_semantic_reconstruction", "loss_generator_diversity")
+    bit_exact_start = True
     for it, (images, labels, masks) in enumerate(batches):
         # dead-work skipping must not change any observable: exercise it on iteration 1
         out = O.train_step(G, D, V, opt_g, opt_d, images, labels, masks, noise[2 * it], noise[2 * it + 1],
@@ -46,7 +47,9 @@ def test_train_step_matches_reference_loop(tag):
         for j, key in ((2 * it, "images_fake_d"), (2 * it + 1, "images_fake_g")):
             s = out[key].flatten()[pix_idx].numpy()
             ref = arr["fake_samples"][j]
-            assert np.abs(s - ref).max() <= 1e-4 * np.abs(ref).max(), (key, it)
+            err = np.abs(s - ref).max()
+            bit_exact_start = bit_exact_start and (it > 0 or err == 0)
+            assert err <= gu.pixel_tolerance(it, bit_exact_start) * np.abs(ref).max(), (key, it, err)
         for key, grads in (("grads_d", out["grads_d"]), ("grads_g", out["grads_g"])):
             norms = np.array([float(g.double().norm()) for g in grads])
             ref = arr[key + "_norms"][it]
@@ -104,7 +107,8 @@ def test_storage_noise_model_is_neither_vacuous_nor_exact():
     lose - pinned to a window, so that a model that stopped rounding (a bound of zero) or rounds wildly (a vacuous bound) fails here."""
     tag = "step_cf4_b4_seed1"
     exact = gu.storage_noise_model(tag, None)
-    assert max(exact["pixel_max"]) <= 1e-4 and max(exact["loss_rel"]) <= 1e-5, exact
+    assert all(e <= gu.pixel_tolerance(it, exact["pixel_max"][0] == 0) for it, e in enumerate(exact["pixel_max"])), exact
+    assert max(exact["loss_rel"]) <= 1e-5, exact
     bf = gu.storage_noise_model(tag, torch.bfloat16)
     assert 2e-3 <= max(bf["pixel_rms"]) <= 2e-2 and 1e-4 <= max(bf["loss_rel"]) <= 5e-3 and max(bf["pixel_max"]) <= 0.12, bf
     h = gu.storage_noise_model(tag, torch.float16, 65536.0)
