@@ -587,6 +587,46 @@ int sp_adam_multi_guarded(const sp_adam_chunk* chunks_dev, int32_t n_chunks, dou
                           double weight_decay, const float* skip_if_nonzero, sp_stream_t stream);
 int sp_loss_scale_update(float* state, float growth, float backoff, int32_t interval, sp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FID: the Inception-v3 feature extractor (torchvision's Inception3, eval mode, transform_input=False) that
+ * /root/reference/frechet_inception_distance.py:11-42 hooks at Mixed_7c, forward only (inception.hip).
+ *
+ * sp_conv2d_general: one BasicConv2d (conv without bias -> BatchNorm2d(eps=0.001) -> ReLU) with the BatchNorm folded into
+ * the packed weights and `bias` on the host - every one of the network's 94 convolutions, the forms torch.nn.Conv2d takes
+ * inside torchvision's InceptionA..E and stem (1x1, 3x3, 5x5, 1x7 / 7x1, 1x3 / 3x1; stride 1 or 2; padding per axis):
+ *   y[n, oy, ox, co] = act( sum_{ky,kx,c} x[n, oy*stride_h - pad_h + ky, ox*stride_w - pad_w + kx, c] * w[co][ky*kw + kx][c] + bias[co] )
+ * oh = (h + 2 pad_h - kh) / stride_h + 1, ow likewise.  x: [n][h][w][ldx] (channels [0, cin_p) read; cin_p % 8 == 0, the 3-channel
+ * image is padded to 8), w: [cout][kh*kw][cin_p], y: [n][oh][ow][ldy] - `y` may point INTO a wider tensor (the channel slice of an
+ * Inception block's concat, torch.cat(outputs, 1)): channels outside [0, cout) of each row are never written.  cout % 4 == 0,
+ * ldy % 4 == 0, kh, kw <= 7, pad < k, act NONE / RELU, x and w 16-byte aligned, y 4-element aligned.  dtype SP_F32 (exact f32
+ * MFMA) / SP_BF16 / SP_F16.  struct_bytes must be sizeof(sp_conv_general_params): a caller built against another layout gets
+ * SP_ERR_INVALID instead of a misread struct.  Shapes outside the contract: SP_ERR_INVALID, dtypes: SP_ERR_UNSUPPORTED. */
+typedef struct sp_conv_general_params {
+    int32_t struct_bytes;   /* sizeof(sp_conv_general_params) */
+    int32_t dtype;
+    const void* x;
+    const void* w;
+    const float* bias;      /* [cout] or NULL */
+    void* y;
+    int32_t n, h, w_, cin_p, ldx, cout, ldy, kh, kw, stride_h, stride_w, pad_h, pad_w, act;
+} sp_conv_general_params;
+int sp_conv2d_general(const sp_conv_general_params* p, sp_stream_t stream);
+/* F.max_pool2d(kernel_size=3, stride=2) (Inception3's stem and InceptionB / InceptionD's pool branch): x [n][h][w][ldx] ->
+ * y [n][(h-3)/2+1][(w-3)/2+1][ldy], channels [0, c); y may be a channel slice of a wider tensor.  c, ldx, ldy % 4 == 0. */
+int sp_maxpool3s2_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t n, int32_t h, int32_t w_, int32_t c, int32_t dtype,
+                      sp_stream_t stream);
+/* F.avg_pool2d(kernel_size=3, stride=1, padding=1) with count_include_pad=True (the divisor is always 9): the pool branch of
+ * InceptionA / C / E.  x, y: [n][h][w][c], c % 4 == 0. */
+int sp_avgpool3s1_fwd(const void* x, void* y, int32_t n, int32_t h, int32_t w_, int32_t c, int32_t dtype, sp_stream_t stream);
+/* Input preparation of frechet_inception_distance.py:71-77,92-96: misc.normalize_m1_1_batch (min / max over each WHOLE image,
+ * no eps: 2 * ((x - min) / (max - min)) - 1) then F.interpolate(size=(oh, ow), mode='bilinear', align_corners=False) in fp32.
+ * x: [n][c][h][w] fp32 (NCHW), minmax: 2n floats of scratch (left holding each image's min, max), y: [n][oh][ow][cp] in dtype,
+ * channels [c, cp) zero; cp % 8 == 0. */
+int sp_inception_prep(const float* x, float* minmax, void* y, int32_t n, int32_t c, int32_t h, int32_t w_, int32_t oh, int32_t ow,
+                      int32_t cp, int32_t dtype, sp_stream_t stream);
+/* F.adaptive_avg_pool2d(Mixed_7c, (1, 1)).view(B, 2048) (frechet_inception_distance.py:38-41): x [n][hw][c] in dtype -> y [n][c] fp32. */
+int sp_global_avgpool_f32(const void* x, float* y, int32_t n, int32_t hw, int32_t c, int32_t dtype, sp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,19 @@ class SpConvParams(ctypes.Structure):
                 ("pool_idx", ctypes.c_void_p), ("split_sync", ctypes.c_void_p)]
 
 
+class SpConvGeneralParams(ctypes.Structure):
+    """sp_conv_general_params (include/sempyr.h): the Inception-v3 convolution's own struct; struct_bytes is checked by the library."""
+    _fields_ = [("struct_bytes", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("n", ctypes.c_int32), ("h", ctypes.c_int32), ("w_", ctypes.c_int32), ("cin_p", ctypes.c_int32),
+                ("ldx", ctypes.c_int32), ("cout", ctypes.c_int32), ("ldy", ctypes.c_int32), ("kh", ctypes.c_int32),
+                ("kw", ctypes.c_int32), ("stride_h", ctypes.c_int32), ("stride_w", ctypes.c_int32), ("pad_h", ctypes.c_int32),
+                ("pad_w", ctypes.c_int32), ("act", ctypes.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=ctypes.sizeof(SpConvGeneralParams), **kw)
+
+
 class SpSnLayer(ctypes.Structure):
     _fields_ = [("w", ctypes.c_void_p), ("u", ctypes.c_void_p), ("v", ctypes.c_void_p),
                 ("scratch_off", ctypes.c_int64), ("part_off", ctypes.c_int64), ("fwd_off", ctypes.c_int64),

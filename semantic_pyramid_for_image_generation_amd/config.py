@@ -31,6 +31,8 @@ results beyond floating-point summation order.  The kernel library itself reads 
     defer_wgrad_reduce    SP_DEFER_WGRAD_REDUCE  1        the slab reductions of the streaming weight-gradient launches of a backward pass in ONE launch at its end (sp_wgrad_reduce_defer / _flush)
     f16_loss_scale        SP_F16_LOSS_SCALE      65536    static loss scale of the fp16 storage mode (ops.set_compute_dtype(torch.float16))
     vgg_fp8               SP_VGG_FP8             0        BASELINE.json config 5's fp8 slice: VGG-16's wide 3x3 layers on the fp8 MFMA in the no-gradient pass (ops.set_vgg_fp8)
+    inception_weights     SP_INCEPTION_WEIGHTS   ""       path of a torchvision inception_v3 state dict: ModelWrapper.validate() computes the FID with it
+                                                          (inception.InceptionV3Features); empty = validate() returns nan
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -70,6 +72,7 @@ class Config:
     bn_pair: bool = True
     bn_pair_upsample: bool = True
     defer_wgrad_reduce: bool = True
+    inception_weights: str = ""
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -84,7 +87,8 @@ class Config:
                    vgg_pool_idx=_flag("SP_VGG_POOL_IDX", True), g_pair=_flag("SP_G_PAIR", True),
                    fuse_tail_grad=_flag("SP_FUSE_TAIL_GRAD", True), vgg_fc_joint=_flag("SP_VGG_FC_JOINT", True),
                    sn_skip_pack=_flag("SP_SN_SKIP_PACK", True), bn_pair=_flag("SP_BN_PAIR", True),
-                   bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True))
+                   bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True),
+                   inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""))
 
 
 CFG = Config.from_env()

@@ -9,9 +9,10 @@ What differs from the reference, without changing any observable result (SURVEY.
     calls (model_wrapper.py:192-202);
   * multi-GPU is one process per GPU with an RCCL all-reduce of the gradients (``distributed.GradientReducer``)
     instead of single-process nn.DataParallel (main.py:91-94).
-Validation (FID with a downloaded Inception-v3) and the sample-grid plots are outside the hot path
-(SURVEY.md section 2, rows 8-9): ``validate`` returns nan; ``inference`` writes the reference's 7 x 7 sample grid as a PNG
-(misc.save_image_grid - torchvision is not a dependency).
+``validate`` computes the FID (fid.frechet_inception_distance) with an Inception-v3 on the library's kernels
+(inception.InceptionV3Features) when it has weights - the constructor's ``inception`` keyword or SP_INCEPTION_WEIGHTS, a
+torchvision inception_v3 state dict - and returns nan without them; ``inference`` writes the reference's 7 x 7 sample grid as a
+PNG (misc.save_image_grid - torchvision is not a dependency).
 """
 from __future__ import annotations
 
@@ -46,7 +47,8 @@ class ModelWrapper(object):
                  semantic_reconstruction_loss: nn.Module = None,
                  diversity_loss: nn.Module = None,
                  save_data_path: Optional[str] = 'saved_data',
-                 gradient_reducer=None) -> None:
+                 gradient_reducer=None,
+                 inception=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -62,6 +64,7 @@ class ModelWrapper(object):
         self.diversity_loss = diversity_loss if diversity_loss is not None else DiversityLoss()
         self.latent_dimensions = self.generator.latent_dimensions
         self.gradient_reducer = gradient_reducer
+        self._inception = inception                # InceptionV3Features, a weights path, or None (CFG.inception_weights)
         for parameter in self.vgg16.parameters():            # model_wrapper.py:67-68
             parameter.requires_grad = False
         self.logger = misc.Logger()
@@ -686,9 +689,28 @@ class ModelWrapper(object):
         self.progress_bar.close()
 
     @torch.no_grad()
-    def validate(self) -> float:
-        """FID needs a downloaded Inception-v3 (frechet_inception_distance.py:22) - outside the hot path."""
-        return float('nan')
+    def validate(self, device: str = 'cuda') -> float:
+        """model_wrapper.py:231-244: the FID over the validation loader, generator in eval mode and back in train mode afterwards.
+        The Inception-v3 weights are the constructor's ``inception`` or else CFG.inception_weights (SP_INCEPTION_WEIGHTS); with
+        neither (or no validation loader) the result is nan.  `device` is accepted for main.py:111's call and ignored: the
+        networks run where the generator's parameters are."""
+        src = self._inception if self._inception is not None else (CFG.inception_weights or None)
+        if src is None or self.validation_dataset_fid is None:
+            return float('nan')
+        from .fid import frechet_inception_distance
+        from .inception import InceptionV3Features
+        if not isinstance(src, InceptionV3Features):
+            src = InceptionV3Features(src)
+            self._inception = src                  # built once
+        dev = next(self.generator.parameters()).device
+        self.generator.eval()
+        self.vgg16.eval()
+        try:
+            fid = frechet_inception_distance(dataset_real=self.validation_dataset_fid, generator=self.generator, vgg16=self.vgg16,
+                                             device=dev, inception=src)
+        finally:
+            self.generator.train()
+        return float(fid)
 
     @torch.no_grad()
     def inference(self, device: str = 'cuda') -> None:
