@@ -2,7 +2,7 @@
 """Benchmark of the hot path: images/sec of one full discriminator + generator training step
 (/root/reference/model_wrapper.py:131-190 semantics incl. both Adam steps) on synthetic 256x256 batches.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: the script starts its own N ranks (one process per GPU, spawned BEFORE the parent touches the GPU; the parent only
 relays rank 0's JSON line) unless it already runs under ``python -m torch.distributed.run`` (RANK / WORLD_SIZE set), in which
@@ -15,7 +15,12 @@ the full record (per-route tables, families, notes, parity sub-objects) goes to 
 `value` is the K timed steps of the contract, taken right after the >= 6 s `sustained` window on the same job (clocks settled).
 --dump-outputs DIR: after the K steps, one more step of the same path from the seeded start writes what it returned (dump_outputs()),
 so that runs and builds can be compared output for output on identical inputs.
-Beside the headline the full record carries (N = 1 only):
+A plain run does only what the headline needs: set-up, the `sustained` window (it settles the clocks the K steps are measured at),
+the W + K steps, the dump, the line.  What is measured or checked beside it, in steps or runs of its own or through a child process,
+comes with --full:
+  box                 the rocm-smi snapshot (sysfs clocks and power are read in every run)
+  multi_gpu           N > 1: allreduce_ms / exposed_ms from 5 extra steps with events around every collective
+and (N = 1 only):
   roofline            achieved / frac: the dominant kernel; conv_frac: FLOP-weighted over every convolution launch (families: forward /
                       input gradient / weight gradient, event-timed on the launch stream in eager steps); sn3x3_bwd: the north-star's
                       3x3 spectral-norm backward; step_frac: the whole step on EXECUTED FLOPs; nonconv_floor_ms measured in the run
@@ -66,10 +71,16 @@ def parse():
                                                       "layers in the no-gradient pass (ops.set_vgg_fp8(1)); with --dtype fp16 this is the config-5 line")
     p.add_argument("--deterministic", action="store_true",
                    help="SP_TUNE_DETERMINISTIC=1: every reduction in a fixed order also in the 16-bit modes (no fp32 atomics in the small-map "
-                        "weight gradients): two runs give identical bits; the default line reports this mode's cost as `deterministic`")
+                        "weight gradients): two runs give identical bits; the --full line reports this mode's cost as `deterministic`")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline does not need: the per-launch kernel probe (roofline), the "
+                        "sub-records (fp16, fp32 parity mode, batch 32, deterministic, channel_factor 2 / 0.5), the parity records, "
+                        "the CPU baseline, the rocm-smi snapshot and, with N > 1, the collectives' timing; the --no-* options "
+                        "below leave parts of it out")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-kernel-probe", action="store_true")
-    p.add_argument("--no-sub-records", action="store_true", help="skip the fp32 parity-mode and batch-32 sub-records")
+    p.add_argument("--no-sub-records", action="store_true",
+                   help="skip the sustained window and (--full) the sub-records and parity records")
     p.add_argument("--device-masks", action="store_true",
                    help="draw a fresh batch of training masks ON THE DEVICE every step (synthetic.training_masks_device, SURVEY.md "
                         "row f1) inside the timed region instead of reusing one resident batch")
@@ -883,6 +894,8 @@ def compact_line(detail: dict) -> dict:
     `detail` (bench_detail.json, stderr).  Pure function of the full record (tests/test_bench_line.py holds it under COMPACT_LIMIT)."""
     line = {k: detail.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                         "scaling", "vs_baseline", "dtype", "data")}
+    if "full" in detail:
+        line["full"] = detail["full"]               # false: the records below that --full adds are absent, not failed
     cfg = detail.get("config") or {}
     line["config"] = {k: cfg.get(k) for k in ("workload", "global_batch", "parallelism", "launch") if k in cfg}
     if cfg.get("collectives"):
@@ -978,7 +991,7 @@ def main():
     backend = os.environ.get("BENCH_DIST_BACKEND", "nccl")
     if one_device:
         local_rank = 0
-    smi = rocm_smi_snapshot() if (rank == 0 and os.environ.get("BENCH_NO_SMI", "0") != "1") else {}    # a child process, BEFORE the first GPU call
+    smi = rocm_smi_snapshot() if (args.full and rank == 0 and os.environ.get("BENCH_NO_SMI", "0") != "1") else {}    # a child process, BEFORE the first GPU call
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     import torch.distributed as dist
@@ -1030,7 +1043,7 @@ def main():
     probe = None
     probe_error = None
     peak = PEAK_TFLOPS[args.dtype]
-    if not args.no_kernel_probe:
+    if args.full and not args.no_kernel_probe:
         try:
             probe = kernel_probe(job.eager_step, peak, steps=5, step_ms=elapsed / args.steps * 1e3)   # the probe brackets individual launches: eager steps
         except RuntimeError as exc:          # (raised after the probe's steps have run: the ranks are still in step with each other)
@@ -1039,7 +1052,7 @@ def main():
         if world > 1:
             dist.barrier()
     launch_mode = job.launch_mode
-    comm = job.comm_stats() if world > 1 else None
+    comm = job.comm_stats() if args.full and world > 1 else None
     grad_bytes = {k: 4 * int(bk.flat.numel()) for k, bk in job.mw._banks.items() if bk.flat is not None}
     rank_elapsed = job.rank_elapsed
     job.close()
@@ -1052,7 +1065,7 @@ def main():
             "metric": "images/sec full G+D train step, 256x256, bs/GPU=%d" % args.batch,
             "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
+            "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": "Semantic-Pyramid GAN D+G step, channel_factor=%g, 256x256x3, batch %d/GPU, Adam lr 1e-5, "
                                    "random-init G/D, kaiming-init frozen VGG-16" % (cf, args.batch),
                        "global_batch": args.batch * world, "parallelism": "dp%d" % world,
@@ -1107,7 +1120,7 @@ def main():
             traffic, prov = recorded_traffic((DOMINANT_KERNEL_SYMBOL, "conv3x3_pp_kernel<bf16, 8", "conv3x3_tall_kernel<bf16, 2, 8>"))
             line["roofline"]["traffic"] = traffic
             line["roofline"]["traffic_source"] = prov
-        subs = world == 1 and not args.no_sub_records
+        subs = args.full and world == 1 and not args.no_sub_records
         graphs = not args.no_graphs
         if subs and args.dtype == "bf16":
             # the 16-bit storage mode that is eight times closer to the fp32 reference at ~99 % of the bf16 speed, FIRST after the headline
@@ -1155,7 +1168,7 @@ def main():
                     line[key]["note"] = "BASELINE.json config 4 (/root/reference/models.py:34-48,117-128: the factor divides), one GPU, batch %d" % args.batch
                 except Exception as exc:
                     line[key] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cf)
             ref20 = line["cpu_baseline"].pop("_ref20", None)
             if ref20 is not None:

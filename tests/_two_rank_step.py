@@ -276,7 +276,7 @@ def launch(out_path, world=2, timeout_s=900.0):
         env = dict(os.environ, BENCH_ONE_DEVICE="1", BENCH_DIST_BACKEND="gloo", BENCH_RANK_TIMEOUT_S="600")
         env.pop("RANK", None); env.pop("WORLD_SIZE", None)
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4",
-                              "--channel-factor", "8", "--no-cpu-baseline", "--no-sub-records", "--no-kernel-probe"],
+                              "--channel-factor", "8", "--full", "--no-cpu-baseline", "--no-sub-records", "--no-kernel-probe"],
                              env=env, capture_output=True, text=True, timeout=900)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         merged["bench_two_ranks"] = {"returncode": out.returncode, "line": json.loads(line[-1]) if line else None,

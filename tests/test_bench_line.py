@@ -100,6 +100,19 @@ def test_parse_steps_and_dump_dir(monkeypatch):
         bench.parse()
 
 
+def test_full_is_off_by_default_and_reported(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    args = bench.parse()
+    assert args.full and args.no_cpu_baseline
+    d = _detail()
+    assert "full" not in bench.compact_line(d)                # a record from before the option
+    d["full"] = False
+    line = bench.compact_line(d)
+    assert line["full"] is False and line["value"] == d["value"] and line["ms_per_step"] == d["ms_per_step"]
+
+
 def test_dpm_level_parsing():
     levels, cur = bench._dpm_levels("0: 132Mhz \n1: 1700Mhz *\n2: 2400Mhz \n")
     assert levels == [132, 1700, 2400] and cur == 1700
