@@ -1,6 +1,8 @@
-// Pieces shared by the implicit-GEMM convolution kernels (conv_igemm.hip, conv_pp.hip): MFMA wrappers, compile-time loops,
-// the epilogues (bias / activation-derivative mask / residuals / activation / 2x2 pooling) and the inline-asm LDS / wait helpers.
+// Pieces shared by the implicit-GEMM convolution kernels (conv_igemm.hip, conv_pp.hip, conv_ppw.hip): MFMA wrappers, compile-time
+// loops, the epilogues (bias / activation-derivative mask / residuals / activation / 2x2 pooling), the ping-pong kernels' work items
+// and tail split, and the inline-asm LDS / wait helpers.
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -235,6 +237,124 @@ __device__ __forceinline__ void conv_epilogue_pool2_idx(const sp_conv_params& p,
     p.pool_idx[ppix * (p.cout >> 4) + (co >> 4)] = idx;
     conv_epilogue16<T>(p, v, ppix, co, false);                            // (bias already added; no scale, mask or residuals with pool2 == 2)
 }
+
+// the kernels' buffer descriptors take 32-bit byte offsets: both operands (n*h*w*cin_p, cout*k*k*cin_p elements of `esz` bytes) below 1 GiB
+inline bool conv_operands_below_1g(const sp_conv_params& p, long esz) {
+    return (long)p.n * p.h * p.w_ * p.cin_p * esz < (1L << 30) && (long)p.cout * p.ksize * p.ksize * p.cin_p * esz < (1L << 30);
+}
+
+// Work items of the ping-pong forms on these dims, 0 where the form does not take them: the admission of its launcher on the dims
+// (sp_conv_pp_launch / sp_conv_ppw_covers add the epilogue's), shared with sp_conv2d_workspace().
+inline long pp_items_8row(int n, int h, int w, int cout) {            // conv_pp.hip: 128 co x 8 x 32 px
+    return h % 8 != 0 || w % 32 != 0 || cout <= 64 ? 0 : (long)n * (h / 8) * (w / 32) * ((cout + 127) / 128);
+}
+inline long pp_items_16row(int n, int h, int w, int cout) {           // conv_pp.hip: 64 co x 16 x 32 px
+    return h % 16 != 0 || w % 32 != 0 || cout <= 16 || cout > 64 ? 0 : (long)n * (h / 16) * (w / 32);
+}
+inline long pp_items_w16(int n, int h, int w, int cout) {             // conv_pp.hip: 128 co x 16 x 16 px, maps 16 wide, >= 64 items
+    const long items = (long)n * (h / 16) * ((cout + 127) / 128);
+    return w != 16 || h % 16 != 0 || cout <= 64 || items < 64 ? 0 : items;
+}
+inline long ppw_items(int n, int h, int w, int cout) {                // conv_ppw.hip: 128 co x 16 x 32 px
+    return h % 16 != 0 || w % 32 != 0 || cout <= 64 ? 0 : (long)n * (h / 16) * (w / 32) * ((cout + 127) / 128);
+}
+
+// ---- K-split of the LAST, partial round of a ping-pong launch ("tail split"; the scheme and its hand-over: the top of conv_pp.hip).
+// The plan serves the launchers and sp_conv2d_workspace(), the piece decoding below the kernels.
+constexpr int SK_NUM_CU = 256;                // MI355X: the persistent ping-pong kernels run one block per CU
+constexpr int SK_MAX_PARTS = 4;
+// The last round takes `chunk` per 32-channel chunk of its longest piece plus, per piece handed over, `near` (two full rounds or more
+// in front of the owner's piece hide more of it) or `far`; a piece is `slab_floats` fp32 values (8 waves x 64 lanes x accumulators).
+struct TailSplitModel { long chunk, near, far; int slab_floats; };
+// conv_pp.hip's items, 64 accumulators: ~3.7 us per chunk, 4 - 6 us per piece handed over - the slabs of P - 1 contributors drain
+// through the memory side, the owner fetches them one round trip each (measured, profiles/README.md round 6)
+constexpr TailSplitModel SK_PP = {37, 40, 60, 8 * 64 * 64};
+// conv_ppw.hip's 16-row items, 128 accumulators: ~1.8 x an 8-row item (6.7 us per chunk), a piece handed over ~1.5 x (twice the
+// bytes, the same latency chain)
+constexpr TailSplitModel SK_PPW = {67, 60, 90, 8 * 64 * 128};
+
+struct TailSplit { int parts, tail_items, grid; };
+// the plan for `total` items of `kchunks` chunks each; parts <= 1: no split (grid: the unsplit launch's).  total < 256 (less than one
+// round: e.g. 80 items of 128 co x 16 x 16 px for 512 -> 512 on 16 x 16 maps at batch 20): every item is a tail item and the grid is
+// tail_items * parts blocks of one piece each (SP_TUNE_CONV_PP_SPLIT = 2 keeps the split to launches of at least one full round).
+inline TailSplit tail_split_plan(int total, int kchunks, const TailSplitModel& m, long workspace_bytes) {
+    TailSplit r{0, 0, total < SK_NUM_CU ? total : SK_NUM_CU};
+    // (less than one round: one block per item - rounded down to a multiple of 8 for the XCD remap, 100 items became 96 blocks of
+    // which four took two items, i.e. two rounds; the kernels skip the remap when the grid is not a multiple of 8)
+    const int mode = sp_tune(SP_TUNE_CONV_PP_SPLIT, 1);
+    if (!mode || total <= 0 || (total < SK_NUM_CU && mode == 2)) return r;
+    const int R = total % SK_NUM_CU;
+    if (R == 0) return r;
+    int pmax = SK_NUM_CU / R;
+    if (pmax > SK_MAX_PARTS) pmax = SK_MAX_PARTS;
+    // a piece has at least two chunks, and the split must save at least a twentieth of the round
+    int P = 1;
+    long best = m.chunk * kchunks;
+    const long handover = total >= 2 * SK_NUM_CU ? m.near : m.far;
+    for (int q = 2; q <= pmax && kchunks / q >= 2; ++q) {
+        const long c = m.chunk * ((kchunks + q - 1) / q) + handover * (q - 1);
+        if (c < best && 20 * c < 19 * m.chunk * kchunks) { best = c; P = q; }
+    }
+    if (P < 2 || (long)R * P * m.slab_floats * 4 > workspace_bytes) return r;
+    r.parts = P; r.tail_items = R;
+    r.grid = total < SK_NUM_CU ? R * P : SK_NUM_CU;
+    return r;
+}
+// sp_conv2d_workspace(): bytes of fp32 scratch with which a launch of `items` items splits its last round (0: it would not)
+inline long tail_split_bytes(long items, int kchunks, const TailSplitModel& m) {
+    if (items >= (1L << 30)) return 0;
+    const TailSplit sk = tail_split_plan((int)items, kchunks, m, 1L << 40);
+    return (long)sk.tail_items * sk.parts * m.slab_floats * 4;
+}
+// the kernels' sk_arg: pieces per tail item; bit 8 with SP_TUNE_CONV_PP_SPLIT = 3 (tests): the closing piece stores and counts like
+// every other piece, so the re-read order runs on every split launch
+inline int tail_split_arg(const TailSplit& sk) { return sk.parts | (sp_tune(SP_TUNE_CONV_PP_SPLIT, 1) == 3 ? 256 : 0); }
+
+// dispatch(): what a launch of `total` 8-row items (conv_pp.hip) costs, in hundredths of the time of one item on every CU - whole rounds
+// without the split; with it the longest piece of the last round plus the hand-over of the partial tiles.  This price does not follow
+// the plan exactly: it takes 100 / P of an item for the longest piece where the plan takes ceil(kchunks / P) / kchunks, and prices a
+// hand-over at 162 / kchunks (the far cost, 60 / 37) also where the plan takes the near one (total >= 512).  Making the two agree moves
+// launches between the 8-row and the 16-row kernel: a change to measure on its own.
+inline long pp_rounds100(long total, int cin_p, long workspace_bytes) {
+    const int kchunks = (cin_p + 31) / 32;
+    if (total < (1L << 30)) {
+        const TailSplit sk = tail_split_plan((int)total, kchunks, SK_PP, workspace_bytes);
+        if (sk.parts > 1 && total >= SK_NUM_CU) return 100 * (total / SK_NUM_CU) + 100 / sk.parts + 162 * (sk.parts - 1) / kchunks + 1;
+    }
+    return 100 * ((total + SK_NUM_CU - 1) / SK_NUM_CU);
+}
+
+// The piece decoding in the kernels: sk_arg first thing, then (assign) the block's share - the first full_total items go round robin as
+// ever (`bid`: the XCD-remapped block index of a grid of `grid`), the rest in K pieces: piece `part` of tail item j runs on the block
+// with the PHYSICAL index j * parts + part.  The order of these steps and of the locals in assign() is the order the kernels were
+// tuned with: it decides the code the compiler emits for them, register allocation included.
+struct TailPiece {
+    int parts;                      // pieces per tail item (0 / 1: no split)
+    bool peek;                      // the closing piece looks at the counter first (tail_split_arg)
+    int my_items;                   // this block's full items
+    bool has_tail;                  // its tail piece, if any:
+    int item, j, part, k0, k1;      //   item number (-1: none), tail index, piece, chunks [k0, k1)
+    bool owner;                     // the piece that adds the others and runs the epilogue
+    int nchunks;                    // the block's chunks of work
+
+    __device__ __forceinline__ explicit TailPiece(int sk_arg) : parts(sk_arg & 255), peek(!(sk_arg & 256)) {}
+    __device__ __forceinline__ void assign(int total, int grid, int bid, int kchunks) {
+        const int full_total = parts > 1 ? (total / grid) * grid : total;
+        my_items = (full_total - bid + grid - 1) / grid;
+        int t_j = 0, t_k1 = 0, t_k0 = 0, t_part = 0, t_item = -1;
+        if (parts > 1 && (int)blockIdx.x < (total - full_total) * parts) {
+            t_j = (int)blockIdx.x / parts;
+            t_part = (int)blockIdx.x - t_j * parts;
+            t_item = full_total + t_j;
+            t_k0 = t_part * kchunks / parts;
+            t_k1 = (t_part + 1) * kchunks / parts;
+        }
+        item = t_item; part = t_part; k0 = t_k0; k1 = t_k1; j = t_j;
+        has_tail = t_item >= 0;
+        owner = t_part == parts - 1;
+        nchunks = my_items * kchunks + (has_tail ? t_k1 - t_k0 : 0);
+    }
+};
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 template <int OFF> __device__ __forceinline__ void lds_rd128(uint4& d, unsigned addr) {

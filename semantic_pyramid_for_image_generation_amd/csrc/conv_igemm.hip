@@ -1566,10 +1566,8 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
         // its own instantiations of a fixed set of kernels, so that the hot ones keep their register allocation - 16-bit: the
         // ping-pong kernel's general epilogue (64 co x 16x32 / 128 co x 8x32 tiles); fp32, and what the ping-pong launcher declines:
         // the LDS-DMA tall kernel on the same tiles; Cout <= 64 with h % 16 != 0: the register-staged halo kernel
-        const long esz = p.dtype == SP_F32 ? 4 : 2;
-        const bool fits30 = (long)p.n * p.h * p.w_ * p.cin_p * esz < (1L << 30) && (long)p.cout * 9 * p.cin_p * esz < (1L << 30);
         if (p.cout <= 64 && p.h % TL_TH != 0) return launch_halo<T, 64, 1, true>(p, s);
-        if (!fits30) { sp_set_error("sp_conv2d_igemm: pool_idx needs operands below 1 GiB (n*h*w*cin_p, cout*9*cin_p)"); return SP_ERR_UNSUPPORTED; }
+        if (!conv_operands_below_1g(p, sizeof(T))) { sp_set_error("sp_conv2d_igemm: pool_idx needs operands below 1 GiB (n*h*w*cin_p, cout*9*cin_p)"); return SP_ERR_UNSUPPORTED; }
         if (sizeof(T) == 2 && sp_tune(SP_TUNE_CONV_PP, 1)) {
             const int rc = sp_conv_pp_launch(p, p.cout <= 64 ? 16 : 8, s);
             if (rc != 1) return rc;
@@ -1580,8 +1578,7 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
     if (p.ksize == 3 && (p.cout > 32 || thin_big) && p.h % HALO_TH == 0 && p.w_ % HALO_TW == 0) {
         // persistent tall kernel (half the LDS reads per MFMA, LDS-DMA pipeline across tiles); SP_CONV_TALL=0 disables, 2 forces
         const int tall_mode = sp_tune(SP_TUNE_CONV_TALL, 1);
-        const long esz = p.dtype == SP_F32 ? 4 : 2;
-        const bool fits30 = (long)p.n * p.h * p.w_ * p.cin_p * esz < (1L << 30) && (long)p.cout * 9 * p.cin_p * esz < (1L << 30);
+        const bool fits30 = conv_operands_below_1g(p, sizeof(T));
         const bool tall_ok = tall_mode && fits30 && p.h % TL_TH == 0 && p.w_ % TL_TW == 0;
         if (p.cout <= 64) {
             // bf16, 16 < Cout <= 64 on 16-row patches: the ping-pong schedule with 8 row-pair waves (conv_pp.hip, WCO = 1)
@@ -1592,11 +1589,13 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
             if (tall_ok) return launch_tall<T, 1>(p, s);
             return launch_halo<T, 64, 1>(p, s);
         }
+        // one block per CU for the tall and the ping-pong kernels, so time ~ rounds over the 256 CUs x time per block: bt 16-row
+        // items (rt rounds) or 2 bt 8-row items (rh)
+        const long bt = (long)p.n * (p.h / TL_TH) * (p.w_ / TL_TW) * ((p.cout + 127) / 128);
+        const long rt = (bt + 255) / 256, rh = (2 * bt + 255) / 256;
         // bf16: the ping-pong schedule (conv_pp.hip) on the same two tiles; tile height by the same round count
         const int pp_mode = sizeof(T) == 2 ? sp_tune(SP_TUNE_CONV_PP, 1) : 0;
         if (pp_mode && fits30 && tall_mode <= 1) {
-            const long bt = (long)p.n * (p.h / TL_TH) * (p.w_ / TL_TW) * ((p.cout + 127) / 128);
-            const long rt = (bt + 255) / 256, rh = (2 * bt + 255) / 256;
             int th = (tall_ok && 19 * rt < 10 * rh) ? 16 : 8;
             if (pp_mode == 8 || (pp_mode == 16 && tall_ok)) th = pp_mode;
             // 16-row patches: conv_ppw.hip (64 co x 4 rows per wave, 0.25 LDS reads per MFMA under the ping-pong schedule) where its
@@ -1609,13 +1608,12 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
                 const long ratio = kch >= 12 ? 172 : kch >= 6 ? 185 : kch >= 3 ? 194 : 204;
                 // (the 8-row form splits the items of a last, partial round along K - conv_pp.hip: its cost is no longer whole rounds)
                 const long wsb = (p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0;
-                const long rh100 = sp_conv_pp_rounds100(2 * bt, p.cin_p, wsb);
+                const long rh100 = pp_rounds100(2 * bt, p.cin_p, wsb);
                 // the 16-row form splits its last round too (conv_ppw.hip), but is CHOSEN on whole rounds: priced with its split it
                 // takes a handful of launches the split 8-row form runs within 0 - 6 % of it (256 -> 256 @64^2 x 40: 138 vs 147 us, the
-                // others level) - step-neutral (profiles/round6_ab_ppw_tail_split_step.txt), and ties go to the kernel that is
-                // measured, profiled and tuned as the dominant one.  SP_TUNE_CONV_PPW = 3 prices it with the split.
-                const long rt100 = ppw_mode == 3 ? sp_conv_ppw_rounds100(bt, p.cin_p, wsb) : 100 * rt;
-                if (ppw_mode == 2 || ratio * rt100 < 100 * rh100) {
+                // others level) - step-neutral (profiles/round6_ab_ppw_tail_split_step.txt, round6_ab_ppw_pricing_step.txt), and ties
+                // go to the kernel that is measured, profiled and tuned as the dominant one
+                if (ppw_mode == 2 || ratio * rt < rh100) {                 // (ratio: per cent; rh100: hundredths of a round)
                     const int rc = sp_conv_ppw_launch(p, s);
                     if (rc != 1) return rc;
                 }
@@ -1626,14 +1624,9 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
                 if (rc != 1) return rc;
             }
         }
-        if (tall_ok) {
-            // one block per CU for both kernels, so time ~ rounds over the 256 CUs x time per block; a tall block does twice
-            // the work of a halo block in ~1.9x the time (scratch/bench_tall.py, profiles/README.md): it wins where the
-            // round quantisation favours it (e.g. 160 instead of 320 blocks).
-            const long bt = (long)p.n * (p.h / TL_TH) * (p.w_ / TL_TW) * ((p.cout + 127) / 128);
-            const long rt = (bt + 255) / 256, rh = (2 * bt + 255) / 256;
-            if (tall_mode == 2 || 19 * rt < 10 * rh) return launch_tall<T, 2>(p, s);
-        }
+        // a tall block does twice the work of a halo block in ~1.9x the time (scratch/bench_tall.py, profiles/README.md): it wins where
+        // the round quantisation favours it (e.g. 160 instead of 320 blocks)
+        if (tall_ok && (tall_mode == 2 || 19 * rt < 10 * rh)) return launch_tall<T, 2>(p, s);
         // remaining Cout > 64 layers: the 128 co x 8x32 tile on the LDS-DMA pipeline of the tall kernel (TH = 8; measured 74 ->
         // 67 us per launch in the step, 902 -> 914 img/s) or, with SP_CONV_SHORT=0 / tall_mode 0, on the register-staged halo kernel
         const int short_env = sp_tune(SP_TUNE_CONV_SHORT, 1);
@@ -1652,9 +1645,7 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
     // LDS-DMA kernel: measured faster for the small-spatial 3x3 layers (latency-bound), slower for 1x1 (profiles/README.md);
     // SP_IGEMM_DMA=2 forces it everywhere, 0 disables it
     const int dma_mode = sp_tune(SP_TUNE_IGEMM_DMA, 1);
-    const long esz_ = p.dtype == SP_F32 ? 4 : 2;
-    const bool dma_fits = M * p.cin_p * esz_ < (1L << 30) && (long)p.cout * p.ksize * p.ksize * p.cin_p * esz_ < (1L << 30);
-    if (p.cout > 16 && dma_fits && (dma_mode == 2 || (dma_mode == 1 && p.ksize == 3 && M <= 8192))) {
+    if (p.cout > 16 && conv_operands_below_1g(p, sizeof(T)) && (dma_mode == 2 || (dma_mode == 1 && p.ksize == 3 && M <= 8192))) {
         if (p.cout <= 32) return launch_dma<T, 1, 4, 2, 4>(p, s);        //  32 co x 256 px
         if (p.cout <= 64) return launch_dma<T, 1, 4, 4, 4>(p, s);        //  64 co x 256 px
         if (M <= 8192) {
@@ -1684,14 +1675,17 @@ extern "C" int sp_conv2d_workspace(int32_t n, int32_t h, int32_t w_, int32_t cin
     const long M = (long)n * h * w_;
     const int dma_mode = sp_tune(SP_TUNE_IGEMM_DMA, 1);
     const bool halo_path = ksize == 3 && cout > 32 && h % HALO_TH == 0 && w_ % HALO_TW == 0;
+    const int kchunks = (cin_p + 31) / 32;
     if (halo_path && dtype != SP_F32 && sp_tune(SP_TUNE_CONV_PP, 1)) {
-        // the ping-pong kernel's K-split of its last partial round (conv_pp.hip): partial tiles of the tail items
-        const long b8 = sp_conv_pp_split_workspace(n, h, w_, cin_p, cout), b16 = sp_conv_ppw_split_workspace(n, h, w_, cin_p, cout);
-        *bytes_out = b8 > b16 ? b8 : b16;
+        // the ping-pong kernels' K-split of their last partial round (conv_pp.hip): partial tiles of the tail items, enough for
+        // whichever form dispatch() picks
+        const long b8 = std::max(tail_split_bytes(pp_items_8row(n, h, w_, cout), kchunks, SK_PP),
+                                 tail_split_bytes(pp_items_16row(n, h, w_, cout), kchunks, SK_PP));
+        *bytes_out = std::max(b8, tail_split_bytes(ppw_items(n, h, w_, cout), kchunks, SK_PPW));
         return SP_OK;
     }
     if (ksize == 3 && w_ == 16 && cout > 64 && dtype != SP_F32 && (sp_tune(SP_TUNE_CONV_PP, 1) == 1 || sp_tune(SP_TUNE_CONV_PP, 1) == 3)) {
-        const long b16 = sp_conv_pp_split_workspace_w16(n, h, cin_p, cout);       // the same kernel on 16 x 16-pixel tiles
+        const long b16 = tail_split_bytes(pp_items_w16(n, h, w_, cout), kchunks, SK_PP);      // the same kernel on 16 x 16-pixel tiles
         if (b16 > 0) { *bytes_out = b16; return SP_OK; }
     }
     if (ksize != 3 || halo_path || cout <= 16 || M > 8192 || dma_mode == 0) return SP_OK;

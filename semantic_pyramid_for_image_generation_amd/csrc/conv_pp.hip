@@ -37,15 +37,13 @@
 
 namespace {
 
-constexpr int PP_TW_WIDE = 32;
-constexpr int PP_NUM_CU = 256;                 // MI355X
 constexpr int PP_BIAS_MAX = 1024;              // output channels whose bias fits the LDS copy
 
 // ---- K-split of the LAST, partial round of work items ("tail split", round 6) ----
 // The block is persistent with one block per CU, so a launch takes ceil(items / 256) rounds: 320 items (512 -> 512 on 32 x 32 maps at
 // batch 20) cost two rounds with 3/4 of the chip idle in the second; at the metric's batch of 20 most mid-network layers sit at 1.25 /
-// 2.5 rounds, which batch 32 does not (profiles/README.md, round 6).  With sk_parts = P > 1 the R = items mod 256 items of the last round
-// are cut into P pieces along K (consecutive ranges of channel chunks; P from a cost model, pp_split_plan) and piece q of tail item j
+// 2.5 rounds, which batch 32 does not (profiles/README.md, round 6).  With P > 1 the R = items mod 256 items of the last round are cut
+// into P pieces along K (consecutive ranges of channel chunks; P from a cost model: tail_split_plan, conv_common.h) and piece q of tail item j
 // goes to the block with the physical index j * P + q - the DMA stream runs into a piece like into any other item.  Pieces q < P - 1 are
 // their block's FIRST piece of work, piece P - 1 its block's LAST.  The hand-over is WAIT-FREE: a piece stores its raw fp32
 // accumulators in its own slab of the caller's scratch (sp_conv_params.workspace), lets them land (`s_waitcnt vmcnt(0)`) and raises a
@@ -59,38 +57,6 @@ constexpr int PP_BIAS_MAX = 1024;              // output channels whose bias fit
 // atomics (sc1: through the XCD's L2 to the memory side - the L2s of different XCDs are not coherent for plain accesses); the wave that
 // runs the epilogue zeroes the counter again, so the counters (sp_conv_params.split_sync: the caller's zero-at-rest area, one per
 // stream - the library keeps no device state) are clean whenever no launch is in flight.
-constexpr int PP_SK_MAX_PARTS = 4;
-constexpr int PP_SK_SLAB_FLOATS = 8 * 64 * 64;           // one piece: 8 waves x 64 lanes x 64 accumulator registers = 128 KB
-
-struct PPSplit { int parts, tail_items, grid; };
-// the plan for `total` items of `kchunks` chunks each; parts <= 1: no split (grid: the unsplit launch's).  total < 256 (less than one
-// round: e.g. 80 items of 128 co x 16 x 16 px for 512 -> 512 on 16 x 16 maps at batch 20): every item is a tail item and the grid is
-// tail_items * parts blocks of one piece each (SP_TUNE_CONV_PP_SPLIT = 2 keeps the split to launches of at least one full round).
-inline PPSplit pp_split_plan(int total, int kchunks, long workspace_bytes) {
-    PPSplit r{0, 0, total < PP_NUM_CU ? total : PP_NUM_CU};
-    // (less than one round: one block per item - rounded down to a multiple of 8 for the XCD remap, 100 items became 96 blocks of
-    // which four took two items, i.e. two rounds; the kernels skip the remap when the grid is not a multiple of 8)
-    const int mode = sp_tune(SP_TUNE_CONV_PP_SPLIT, 1);
-    if (!mode || total <= 0 || (total < PP_NUM_CU && mode == 2)) return r;
-    const int R = total % PP_NUM_CU;
-    if (R == 0) return r;
-    int pmax = PP_NUM_CU / R;
-    if (pmax > PP_SK_MAX_PARTS) pmax = PP_SK_MAX_PARTS;
-    // the last round takes ~3.7 us per chunk of its longest piece + 4 - 6 us per piece handed over (measured, profiles/README.md round 6:
-    // the slabs of P - 1 contributors drain through the memory side, the owner fetches them one round trip each); a piece has at
-    // least two chunks, and the split must save at least a twentieth of the round
-    int P = 1;
-    long best = 37L * kchunks;
-    const long handover = total >= 2 * PP_NUM_CU ? 40 : 60;  // (two full items in front of the owner's piece hide more of it)
-    for (int q = 2; q <= pmax && kchunks / q >= 2; ++q) {
-        const long c = 37L * ((kchunks + q - 1) / q) + handover * (q - 1);
-        if (c < best && 20 * c < 19 * 37L * kchunks) { best = c; P = q; }
-    }
-    if (P < 2 || (long)R * P * PP_SK_SLAB_FLOATS * 4 > workspace_bytes) return r;
-    r.parts = P; r.tail_items = R;
-    r.grid = total < PP_NUM_CU ? R * P : PP_NUM_CU;
-    return r;
-}
 
 template <typename T, int WCO, int FW = 2>
 struct PPGeom {
@@ -132,8 +98,7 @@ constexpr int pp_group_index(int h, int dr, int rw) {
 // (scratch: -DPP_ASSUME_SIMPLE), a launch of 128->128 @128^2 drops from 170 K to 148 K cycles per block, 64->128 from 111 K to 92 K.
 template <typename T, int WCO, int PRIO, bool TIMING = false, bool DMA_IN_L = true, bool FAST = false, int FW = 2, bool TAIL = false, bool IDX = false>
 __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int cotiles, int total, int prio, int sk_arg) {
-    const int sk_parts = sk_arg & 255;                      // pieces per tail item (0 / 1: no split); bit 8: the closing piece does not peek (tests)
-    const bool sk_peek = !(sk_arg & 256);
+    TailPiece tp(sk_arg);                                   // tail split (see the top of the file; pieces assigned below)
     static_assert(!IDX || (!FAST && sizeof(T) == 2), "pool_idx: the general 16-bit epilogue");
     static_assert(!TAIL || (FAST && WCO == 1 && FW == 2), "the fused 1x1 tail lives in the 64-channel FAST form");
     using G = PPGeom<T, WCO, FW>;
@@ -156,21 +121,9 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
     const int GR = gridDim.x;
     int bid = blockIdx.x;
     if ((GR & 7) == 0) bid = (bid & 7) * (GR >> 3) + (bid >> 3);
-    // tail split (see the top of the file): the first full_total items go round robin as ever, the rest in K pieces
-    const int full_total = sk_parts > 1 ? (total / GR) * GR : total;
-    const int my_items = (full_total - bid + GR - 1) / GR;
-    int t_item = -1, t_part = 0, t_k0 = 0, t_k1 = 0, t_j = 0;
-    if (sk_parts > 1 && (int)blockIdx.x < (total - full_total) * sk_parts) {
-        t_j = (int)blockIdx.x / sk_parts;
-        t_part = (int)blockIdx.x - t_j * sk_parts;
-        t_item = full_total + t_j;
-        t_k0 = t_part * kchunks / sk_parts;
-        t_k1 = (t_part + 1) * kchunks / sk_parts;
-    }
-    const bool has_tail = t_item >= 0;
-    const bool t_owner = t_part == sk_parts - 1;            // the piece that adds the others and runs the epilogue
-    const int nchunks = my_items * kchunks + (has_tail ? t_k1 - t_k0 : 0);
-    if (nchunks <= 0) return;
+    // tail split (see the top of the file): the first items go round robin as ever, the rest in K pieces
+    tp.assign(total, GR, bid, kchunks);
+    if (tp.nchunks <= 0) return;
 
     // ---- bias -> LDS (fp32, zero padded to whole co-tiles), before the first LDS-DMA is in flight
     {
@@ -216,7 +169,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
     Coords cur, nxt, tailc;
     int s_co, s_tx, s_ty, s_n;
     {
-        int t = has_tail ? t_item : 0;
+        int t = tp.has_tail ? tp.item : 0;
         tailc.co_i = t % cotiles; t /= cotiles;
         tailc.tx_i = t % tiles_x; t /= tiles_x;
         tailc.ty_i = t % tiles_y; tailc.n = t / tiles_y;
@@ -237,10 +190,10 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
         r.n = c.n + s_n + cy;
         return r;
     };
-    // item number `it` of this block: its my_items full items (round robin) with the tail piece in front of them (a contributing piece)
+    // item number `it` of this block: its tp.my_items full items (round robin) with the tail piece in front of them (a contributing piece)
     // or behind them (the piece that owns the item's epilogue)
     int it = 0;
-    const int t_pos = has_tail ? (t_owner ? my_items : 0) : -1;
+    const int t_pos = tp.has_tail ? (tp.owner ? tp.my_items : 0) : -1;
     Coords strided = cur;                                   // the next full item to hand out
     auto item_coords = [&](int idx, bool& is_tail) {
         is_tail = idx == t_pos;
@@ -333,8 +286,8 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
     // ---- prologue: chunk 0's halo, weight stages 0, 1 and 2
     set_halo_desc(cur);
     set_w_desc(cur);
-    int kc = cur_is_tail ? t_k0 : 0;                        // chunk of the current item; a tail piece starts inside its item
-    int kc_end = cur_is_tail ? t_k1 : kchunks;
+    int kc = cur_is_tail ? tp.k0 : 0;                       // chunk of the current item; a tail piece starts inside its item
+    int kc_end = cur_is_tail ? tp.k1 : kchunks;
 #pragma unroll
     for (int i = 0; i < HPW; ++i) issue_halo_piece(i, true, kc * KC, 0);
 #pragma unroll
@@ -345,7 +298,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the bias copy
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    bias_fetch(!(cur_is_tail && !t_owner), cur.co_i * CO_T);   // (a tail piece that only contributes starts from zero)
+    bias_fetch(!(cur_is_tail && !tp.owner), cur.co_i * CO_T);  // (a tail piece that only contributes starts from zero)
     auto acc_from_bias = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -376,12 +329,12 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
     float vmax = 0.f;                                       // SP_F8: running max of this lane's outputs (merged once per block at the end)
     int g4 = 0;                                             // weight ring slot of the stage being computed (stage index mod 4)
     const bool vec_ok = ((p.ldy & 3) == 0) && ((p.cout & 3) == 0);
-    for (int gc = 0; gc < nchunks; ++gc) {
-        const bool more_chunks = gc + 1 < nchunks;
+    for (int gc = 0; gc < tp.nchunks; ++gc) {
+        const bool more_chunks = gc + 1 < tp.nchunks;
         const bool item_ends = kc + 1 == kc_end;
         if constexpr (TIMING) stamp_on = kc != 0 && !item_ends;
         const unsigned hb = (unsigned)((gc & 1) * HALO_BUF);
-        const int c0_next = item_ends ? (nxt_is_tail ? t_k0 * KC : 0) : (kc + 1) * KC;
+        const int c0_next = item_ends ? (nxt_is_tail ? tp.k0 * KC : 0) : (kc + 1) * KC;
         auto stage = [&](auto sc) {
             constexpr int st = decltype(sc)::value;        // stage inside the chunk = tap column
             constexpr int NREAD = 12 + FW * NB;
@@ -468,7 +421,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
             const int co_b = co0 + wco * 64 + (lane >> 4) * 16;          // this lane's 16 consecutive channels
             const bool wide = FAST ? co_b < p.cout : vec_ok && (p.ldy & 7) == 0 && co_b + 16 <= p.cout;
             bool run_epilogue = true;
-            if (cur_is_tail && sk_parts > 1) {                           // wave-uniform
+            if (cur_is_tail && tp.parts > 1) {                           // wave-uniform
                 // tail split, WAIT-FREE: nobody ever waits for another block (two kernels that spin for blocks of their own which the
                 // other one keeps off the CUs deadlock - seen with two ranks sharing one GPU).  A piece stores its raw accumulators in
                 // ITS slab, lets the stores land (vmcnt(0)) and raises the item's per-wave counter; whoever raises it last sums the P
@@ -478,12 +431,12 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
                 int woff = wave * 4096 + lane;
                 asm volatile("" : "+v"(woff));                           // (computed HERE: hoisted out of the chunk loop, the sixty-odd
                                                                          // addresses below stay live across it and spill)
-                float* slab0 = reinterpret_cast<float*>(p.workspace) + ((long)t_j * sk_parts) * PP_SK_SLAB_FLOATS + woff;
-                int* flag = p.split_sync + t_j * 8 + wave;
+                float* slab0 = reinterpret_cast<float*>(p.workspace) + ((long)tp.j * tp.parts) * SK_PP.slab_floats + woff;
+                int* flag = p.split_sync + tp.j * 8 + wave;
                 bool fast = false, last = false;
-                if (t_owner && sk_peek) fast = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sk_parts - 1;
+                if (tp.owner && tp.peek) fast = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tp.parts - 1;
                 if (!fast) {
-                    float* dst = slab0 + (long)t_part * PP_SK_SLAB_FLOATS;
+                    float* dst = slab0 + (long)tp.part * SK_PP.slab_floats;
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -494,14 +447,14 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the slab is at the memory side before the counter says so
                     int old = 0;
                     if (lane == 0) old = __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    last = __builtin_amdgcn_readfirstlane(old) == sk_parts - 1;
+                    last = __builtin_amdgcn_readfirstlane(old) == tp.parts - 1;
                 }
                 run_epilogue = fast || last;
                 // slabs to add, in order: the closing piece's own (kept in registers on the fast path, re-read otherwise), then 0 .. P - 2
-                const int q_first = fast ? 0 : -1, q_end = run_epilogue ? sk_parts - 1 : -1;
+                const int q_first = fast ? 0 : -1, q_end = run_epilogue ? tp.parts - 1 : -1;
 #pragma unroll 1
                 for (int q = q_first; q < q_end; ++q) {
-                    const float* src = slab0 + (long)(q < 0 ? sk_parts - 1 : q) * PP_SK_SLAB_FLOATS;
+                    const float* src = slab0 + (long)(q < 0 ? tp.parts - 1 : q) * SK_PP.slab_floats;
                     // all 64 loads of a slab in flight: one round trip to the memory side per slab; whole fragments (the accumulators are
                     // 4-register tuples: element-wise updates cost conv_ppw.hip, with its 128 accumulators, 300 spilled registers)
                     f32x4_t t[4 * NFR];
@@ -768,11 +721,11 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
             ++it;
             cur = nxt;
             cur_is_tail = nxt_is_tail;
-            kc = cur_is_tail ? t_k0 : 0;
-            kc_end = cur_is_tail ? t_k1 : kchunks;
+            kc = cur_is_tail ? tp.k0 : 0;
+            kc_end = cur_is_tail ? tp.k1 : kchunks;
             nxt = item_coords(it + 1, nxt_is_tail);          // (past the block's last item: coordinates nobody uses)
             stamp(5);
-            bias_fetch(more_chunks && !(cur_is_tail && !t_owner), cur.co_i * CO_T);   // (after the epilogue's own reads of the bias / scale tables)
+            bias_fetch(more_chunks && !(cur_is_tail && !tp.owner), cur.co_i * CO_T);   // (after the epilogue's own reads of the bias / scale tables)
             acc_from_bias();
             stamp(8);
             if (half_b) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
@@ -812,7 +765,11 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
 template <typename T, int WCO, int PRIO, bool TIMING = false, bool DMA_IN_L = true, bool FAST = false, int FW = 2, bool TAIL = false, bool IDX = false>
 int launch_pp(const sp_conv_params& p, int prio, hipStream_t s) {
     using G = PPGeom<T, WCO, FW>;
-    constexpr int TH = G::TH;
+    // the form's admission on the dims and its work items (conv_common.h)
+    const long items = FW == 1 ? pp_items_w16(p.n, p.h, p.w_, p.cout) : WCO == 1 ? pp_items_16row(p.n, p.h, p.w_, p.cout)
+                                                                               : pp_items_8row(p.n, p.h, p.w_, p.cout);
+    if (items == 0) return 1;
+    const int total = (int)items;
     constexpr int LDS_BYTES = TAIL ? G::LDS_TAIL : G::LDS;
     static_assert(LDS_BYTES <= 163840, "LDS budget");
     static bool attr_set = false;
@@ -823,65 +780,26 @@ int launch_pp(const sp_conv_params& p, int prio, hipStream_t s) {
         attr_set = true;
     }
     const int cotiles = (p.cout + G::CO_T - 1) / G::CO_T;
-    const int total = p.n * (p.h / TH) * (p.w_ / G::TW) * cotiles;
     // persistent: one block per CU; the items of a last, partial round split along K where the caller lent the scratch (top of the file)
-    PPSplit sk = pp_split_plan(total, (p.cin_p + G::KC - 1) / G::KC,
-                               (!G::F8 && !TIMING && !TAIL && p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0);
-    const int grid = sk.grid;
+    const TailSplit sk = tail_split_plan(total, (p.cin_p + G::KC - 1) / G::KC, SK_PP,
+                                         (!G::F8 && !TIMING && !TAIL && p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0);
     sp_note_route(G::F8 ? "conv3x3_pp<f8,2>" : FW == 1 ? "conv3x3_pp<16bit,2,FAST,w16>" : WCO == 2 ? (FAST ? "conv3x3_pp<16bit,2,FAST>" : "conv3x3_pp<16bit,2>")
                                                                                   : (FAST ? "conv3x3_pp<16bit,1,FAST>" : "conv3x3_pp<16bit,1>"));
-    // SP_TUNE_CONV_PP_SPLIT = 3 (tests): the closing piece stores and counts like every other piece, so the re-read order runs on every split launch
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS_BYTES, s, p, cotiles, total, prio, sk.parts | (sp_tune(SP_TUNE_CONV_PP_SPLIT, 1) == 3 ? 256 : 0));
+    hipLaunchKernelGGL(kern, dim3((unsigned)sk.grid), dim3(512), LDS_BYTES, s, p, cotiles, total, prio, tail_split_arg(sk));
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
 
 }  // namespace
 
-// sp_conv2d_workspace(): bytes of fp32 scratch with which a 16-bit 3x3 launch of these dims can split its last round (0: it would not)
-long sp_conv_pp_split_workspace(int n, int h, int w, int cin_p, int cout) {
-    if (h % 8 != 0 || w % PP_TW_WIDE != 0 || cout <= 16) return 0;
-    const int kchunks = (cin_p + 31) / 32;
-    long need = 0;
-    auto plan = [&](long total) {
-        if (total >= (1L << 30)) return;
-        const PPSplit sk = pp_split_plan((int)total, kchunks, 1L << 40);
-        const long b = (long)sk.tail_items * (sk.parts > 1 ? sk.parts : 0) * PP_SK_SLAB_FLOATS * 4;
-        if (b > need) need = b;
-    };
-    if (cout <= 64) { if (h % 16 == 0) plan((long)n * (h / 16) * (w / PP_TW_WIDE)); }
-    else plan((long)n * (h / 8) * (w / PP_TW_WIDE) * ((cout + 127) / 128));
-    return need;
-}
-
-// the same for the 16-pixel-wide tiles (128 co x 16 x 16 px per item, maps 16 wide)
-long sp_conv_pp_split_workspace_w16(int n, int h, int cin_p, int cout) {
-    if (h % 16 != 0 || cout <= 64 || (long)n * (h / 16) * ((cout + 127) / 128) < 64) return 0;      // (sp_conv_pp_launch's admission)
-    const PPSplit sk = pp_split_plan(n * (h / 16) * ((cout + 127) / 128), (cin_p + 31) / 32, 1L << 40);
-    return (long)sk.tail_items * (sk.parts > 1 ? sk.parts : 0) * PP_SK_SLAB_FLOATS * 4;
-}
-
-// dispatch(): what a launch of `total` 8-row items costs, in hundredths of the time of one item on every CU - whole rounds without the
-// split; with it the longest piece of the last round plus the hand-over of the partial tiles (pp_split_plan's model)
-long sp_conv_pp_rounds100(long total, int cin_p, long workspace_bytes) {
-    const int kchunks = (cin_p + 31) / 32;
-    if (total < (1L << 30)) {
-        const PPSplit sk = pp_split_plan((int)total, kchunks, workspace_bytes);
-        if (sk.parts > 1 && total >= PP_NUM_CU) return 100 * (total / PP_NUM_CU) + 100 / sk.parts + 162 * (sk.parts - 1) / kchunks + 1;
-    }
-    return 100 * ((total + PP_NUM_CU - 1) / PP_NUM_CU);
-}
-
 // conv_igemm.hip's dispatch(): bf16 3x3 layers with more than 64 output channels on (th x 32)-pixel patches, th = 8 or 16.
 // Returns 1 if the shape is not covered (the caller then keeps its own kernel).
 int sp_conv_pp_launch(const sp_conv_params& p, int th, hipStream_t s) {
     if (p.dtype == SP_F8) {
-        if (p.ksize != 3 || p.cout <= 64 || p.h % 8 != 0 || p.w_ % PP_TW_WIDE != 0 || (long)p.n * p.h * p.w_ * p.cin_p >= (1L << 30) ||
-            (long)p.cout * 9 * p.cin_p >= (1L << 30) || (p.cout + 127) / 128 * 128 > PP_BIAS_MAX) return 1;
+        if (p.ksize != 3 || !conv_operands_below_1g(p, 1) || (p.cout + 127) / 128 * 128 > PP_BIAS_MAX) return 1;
         return launch_pp<f8, 2, 1>(p, 1, s);
     }
-    if (p.dtype != SP_BF16 || p.ksize != 3) return 1;
-    const long esz = 2;
+    if (p.dtype != SP_BF16 || p.ksize != 3 || !conv_operands_below_1g(p, 2)) return 1;
     if (th == 1616) {
         // maps 16 wide (th code 1616): 128 co x 16 x 16 px tiles - one whole image of the 16 x 16 layers per block.  Few items (80 for
         // 512 -> 512 at batch 20), but each runs the ping-pong pipeline on a 128 x 256 tile instead of sixteen 64 x 64 tiles
@@ -889,12 +807,10 @@ int sp_conv_pp_launch(const sp_conv_params& p, int th, hipStream_t s) {
         // 46.8, 256 -> 512: 29.0 -> 25.2; with 40 items (Cout 256) it is no faster - those stay on the igemm.  Split-K over 2-4 K
         // ranges (fp32 partial tiles + the finalize pass) was built and measured: 60 us - a 128 x 256 fp32 tile per 12 stages is
         // more store-path time than the extra parallelism buys
-        if (p.w_ != 16 || p.h % 16 != 0 || (long)p.n * (p.h / 16) * ((p.cout + 127) / 128) < 64 || p.pool2 != 0 || (p.cout & 15) != 0 || (p.ldy & 7) != 0 || p.act == SP_ACT_TANH) return 1;
-        if ((long)p.n * p.h * p.w_ * p.cin_p * esz >= (1L << 30) || (long)p.cout * 9 * p.cin_p * esz >= (1L << 30)) return 1;
+        if (p.pool2 != 0 || (p.cout & 15) != 0 || (p.ldy & 7) != 0 || p.act == SP_ACT_TANH) return 1;
         return launch_pp<bf16, 2, 1, false, true, true, 1>(p, 1, s);
     }
-    if (p.h % th != 0 || p.w_ % PP_TW_WIDE != 0) return 1;
-    if ((long)p.n * p.h * p.w_ * p.cin_p * esz >= (1L << 30) || (long)p.cout * 9 * p.cin_p * esz >= (1L << 30)) return 1;
+    if (th != 8 && th != 16) return 1;
     // SP_TUNE_CONV_PP_PRIO (diagnostics / A-B): bit 2 = the TIMING build (bit 9 with it: stamps of mid-item chunks only),
     // bit 4 = the general epilogue everywhere
     const int prio = sp_tune(SP_TUNE_CONV_PP_PRIO, 1);
@@ -905,18 +821,15 @@ int sp_conv_pp_launch(const sp_conv_params& p, int th, hipStream_t s) {
     }
     if (p.pool_idx != nullptr) {                           // ReLU + MaxPool with recorded window positions: own instantiations (general epilogue)
         if (p.pool2 != 2) return 1;
-        if (th == 16 && p.cout <= 64) return launch_pp<bf16, 1, 1, false, true, false, 2, false, true>(p, prio, s);
-        if (th == 8 && p.cout > 64) return launch_pp<bf16, 2, 1, false, true, false, 2, false, true>(p, prio, s);
-        return 1;
+        return th == 16 ? launch_pp<bf16, 1, 1, false, true, false, 2, false, true>(p, prio, s)
+                        : launch_pp<bf16, 2, 1, false, true, false, 2, false, true>(p, prio, s);
     }
-    if (th == 16 && p.cout <= 64) {                        // 64 co x 16x32 px
-        if ((prio & 4) && fast && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4)
-            return launch_pp<bf16, 1, 1, true, true, true>(p, prio, s);       // (TIMING build, see below)
+    // the TIMING build writes 256 x 8 x 16 floats of stamps into the caller's workspace: only with a workspace that holds them
+    const bool timing = (prio & 4) && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4;
+    if (th == 16) {                                        // 64 co x 16x32 px
+        if (timing && fast) return launch_pp<bf16, 1, 1, true, true, true>(p, prio, s);
         return fast ? launch_pp<bf16, 1, 1, false, true, true>(p, prio, s) : launch_pp<bf16, 1, 1>(p, prio, s);
     }
-    if (th != 8 || p.cout <= 64) return 1;
-    // the TIMING build writes 256 x 8 x 16 floats of stamps into the caller's workspace: only with a workspace that holds them
-    if ((prio & 4) && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4)
-        return fast ? launch_pp<bf16, 2, 1, true, true, true>(p, prio, s) : launch_pp<bf16, 2, 1, true>(p, prio, s);
+    if (timing) return fast ? launch_pp<bf16, 2, 1, true, true, true>(p, prio, s) : launch_pp<bf16, 2, 1, true>(p, prio, s);
     return fast ? launch_pp<bf16, 2, 1, false, true, true>(p, prio, s) : launch_pp<bf16, 2, 1>(p, prio, s);
 }

@@ -29,38 +29,10 @@
 
 namespace {
 
-constexpr int PW_NUM_CU = 256;
 constexpr int PW_BIAS_MAX = 1024;
 
-// ---- K-split of the last, partial round of work items: conv_pp.hip's scheme ("tail split", top of that file) on this kernel's items.
-// A piece is 8 waves x 64 lanes x 128 accumulator registers = 256 KB of fp32; an item takes ~1.8 x an 8-row item of conv_pp.hip
-// (6.7 us per 32-channel chunk), a piece handed over ~1.5 x (twice the bytes, the same latency chain).
-constexpr int PW_SK_MAX_PARTS = 4;
-constexpr int PW_SK_SLAB_FLOATS = 8 * 64 * 128;
-
-struct PWSplit { int parts, tail_items, grid; };
-inline PWSplit pw_split_plan(int total, int kchunks, long workspace_bytes) {
-    PWSplit r{0, 0, total < PW_NUM_CU ? total : PW_NUM_CU};
-    // (less than one round: one block per item - rounded down to a multiple of 8 for the XCD remap, 100 items became 96 blocks of
-    // which four took two items, i.e. two rounds; the kernels skip the remap when the grid is not a multiple of 8)
-    const int mode = sp_tune(SP_TUNE_CONV_PP_SPLIT, 1);
-    if (!mode || total <= 0 || (total < PW_NUM_CU && mode == 2)) return r;
-    const int R = total % PW_NUM_CU;
-    if (R == 0) return r;
-    int pmax = PW_NUM_CU / R;
-    if (pmax > PW_SK_MAX_PARTS) pmax = PW_SK_MAX_PARTS;
-    int P = 1;
-    long best = 67L * kchunks;
-    const long handover = total >= 2 * PW_NUM_CU ? 60 : 90;
-    for (int q = 2; q <= pmax && kchunks / q >= 2; ++q) {
-        const long c = 67L * ((kchunks + q - 1) / q) + handover * (q - 1);
-        if (c < best && 20 * c < 19 * 67L * kchunks) { best = c; P = q; }
-    }
-    if (P < 2 || (long)R * P * PW_SK_SLAB_FLOATS * 4 > workspace_bytes) return r;
-    r.parts = P; r.tail_items = R;
-    r.grid = total < PW_NUM_CU ? R * P : PW_NUM_CU;
-    return r;
-}
+// K-split of the last, partial round of work items: conv_pp.hip's scheme ("tail split", top of that file) on this kernel's items, with
+// their own cost model (SK_PPW, conv_common.h).
 
 template <typename T>
 struct PWGeom {
@@ -79,8 +51,7 @@ struct PWGeom {
 
 template <typename T, bool TIMING = false, bool DMA_LB = true, bool POOL = false>
 __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int cotiles, int total, int prio, int sk_arg) {
-    const int sk_parts = sk_arg & 255;                      // (conv_pp.hip: pieces per tail item; bit 8: the closing piece does not peek)
-    const bool sk_peek = !(sk_arg & 256);
+    TailPiece tp(sk_arg);                                   // tail split (conv_pp.hip; pieces assigned below)
     static_assert(sizeof(T) == 2, "16-bit storage");
     using G = PWGeom<T>;
     constexpr int E = G::E, KC = G::KC, CO_T = G::CO_T, WPX = G::WPX, RW = G::RW, FW = G::FW, NB = G::NB, NFR = G::NFR, HR = G::HR, HP = G::HP, TH = G::TH;
@@ -101,21 +72,9 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
     const int GR = gridDim.x;
     int bid = blockIdx.x;
     if ((GR & 7) == 0) bid = (bid & 7) * (GR >> 3) + (bid >> 3);
-    // tail split (conv_pp.hip): the first full_total items go round robin, the rest in K pieces
-    const int full_total = sk_parts > 1 ? (total / GR) * GR : total;
-    const int my_items = (full_total - bid + GR - 1) / GR;
-    int t_item = -1, t_part = 0, t_k0 = 0, t_k1 = 0, t_j = 0;
-    if (sk_parts > 1 && (int)blockIdx.x < (total - full_total) * sk_parts) {
-        t_j = (int)blockIdx.x / sk_parts;
-        t_part = (int)blockIdx.x - t_j * sk_parts;
-        t_item = full_total + t_j;
-        t_k0 = t_part * kchunks / sk_parts;
-        t_k1 = (t_part + 1) * kchunks / sk_parts;
-    }
-    const bool has_tail = t_item >= 0;
-    const bool t_owner = t_part == sk_parts - 1;
-    const int nchunks = my_items * kchunks + (has_tail ? t_k1 - t_k0 : 0);
-    if (nchunks <= 0) return;
+    // tail split (conv_pp.hip): the first items go round robin, the rest in K pieces
+    tp.assign(total, GR, bid, kchunks);
+    if (tp.nchunks <= 0) return;
 
     // ---- bias -> LDS (fp32, zero padded to whole co-tiles), before the first LDS-DMA is in flight
     {
@@ -143,7 +102,7 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
     Coords cur, nxt, tailc;
     int s_co, s_tx, s_ty, s_n;
     {
-        int t = has_tail ? t_item : 0;
+        int t = tp.has_tail ? tp.item : 0;
         tailc.co_i = t % cotiles; t /= cotiles;
         tailc.tx_i = t % tiles_x; t /= tiles_x;
         tailc.ty_i = t % tiles_y; tailc.n = t / tiles_y;
@@ -165,7 +124,7 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
         return r;
     };
     int it = 0;
-    const int t_pos = has_tail ? (t_owner ? my_items : 0) : -1;     // a contributing piece leads its block, the owning piece closes it
+    const int t_pos = tp.has_tail ? (tp.owner ? tp.my_items : 0) : -1;       // a contributing piece leads its block, the owning piece closes it
     Coords strided = cur;
     auto item_coords = [&](int idx, bool& is_tail) {
         is_tail = idx == t_pos;
@@ -247,8 +206,8 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
     // ---- prologue: chunk 0's halo, weight stages 0 .. LA - 1
     set_halo_desc(cur);
     set_w_desc(cur);
-    int kc = cur_is_tail ? t_k0 : 0;
-    int kc_end = cur_is_tail ? t_k1 : kchunks;
+    int kc = cur_is_tail ? tp.k0 : 0;
+    int kc_end = cur_is_tail ? tp.k1 : kchunks;
 #pragma unroll
     for (int i = 0; i < HPW; ++i) issue_halo_piece(i, true, kc * KC, 0);
 #pragma unroll
@@ -259,7 +218,7 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the bias copy
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    bias_fetch(!(cur_is_tail && !t_owner), cur.co_i * CO_T);
+    bias_fetch(!(cur_is_tail && !tp.owner), cur.co_i * CO_T);
     auto acc_from_bias = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -282,11 +241,11 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
     };
     if constexpr (TIMING) tprev = __builtin_readcyclecounter();
     int g3 = 0;                                             // weight ring slot of the stage being computed (stage index mod 3)
-    for (int gc = 0; gc < nchunks; ++gc) {
-        const bool more_chunks = gc + 1 < nchunks;
+    for (int gc = 0; gc < tp.nchunks; ++gc) {
+        const bool more_chunks = gc + 1 < tp.nchunks;
         const bool item_ends = kc + 1 == kc_end;
         const unsigned hb = (unsigned)((gc & 1) * HALO_BUF);
-        const int c0_next = item_ends ? (nxt_is_tail ? t_k0 * KC : 0) : (kc + 1) * KC;
+        const int c0_next = item_ends ? (nxt_is_tail ? tp.k0 * KC : 0) : (kc + 1) * KC;
         auto stage = [&](auto sc) {
             constexpr int st = decltype(sc)::value;        // stage inside the chunk = tap column
             constexpr int TAP_STRIDE = CO_T * 64;
@@ -395,15 +354,15 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
             // count is zero for everyone else - and sixteen registers per group behind an opaque offset, whole-fragment updates: as
             // an if / else the two paths (accumulators unchanged / updated) met in 128 phi copies and the main loop of this kernel
             // (~245 registers) spilled 300
-            const bool sk_tail = cur_is_tail && sk_parts > 1;           // wave-uniform
+            const bool sk_tail = cur_is_tail && tp.parts > 1;           // wave-uniform
             int woff = wave * 8192 + lane;
             asm volatile("" : "+v"(woff));                               // (keeps the slab addresses out of the chunk loop's live ranges)
-            float* slab0 = reinterpret_cast<float*>(p.workspace) + ((long)t_j * sk_parts) * PW_SK_SLAB_FLOATS + woff;
-            int* flag = p.split_sync + t_j * 8 + wave;
+            float* slab0 = reinterpret_cast<float*>(p.workspace) + ((long)tp.j * tp.parts) * SK_PPW.slab_floats + woff;
+            int* flag = p.split_sync + tp.j * 8 + wave;
             bool sk_fast = false, sk_last = false;
-            if (sk_tail && t_owner && sk_peek) sk_fast = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sk_parts - 1;
+            if (sk_tail && tp.owner && tp.peek) sk_fast = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tp.parts - 1;
             if (sk_tail && !sk_fast) {
-                float* dst = slab0 + (long)t_part * PW_SK_SLAB_FLOATS;
+                float* dst = slab0 + (long)tp.part * SK_PPW.slab_floats;
                 static_for<NFR>([&](auto gc_) {
                     constexpr int g = decltype(gc_)::value;               // accumulators 16 g .. 16 g + 15 = acc[g / 2][4 (g % 2) .. + 3][0..3]
                     int o = g * 16 * 64;
@@ -416,13 +375,13 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the slab is at the memory side before the counter says so
                 int old = 0;
                 if (lane == 0) old = __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                sk_last = __builtin_amdgcn_readfirstlane(old) == sk_parts - 1;
+                sk_last = __builtin_amdgcn_readfirstlane(old) == tp.parts - 1;
             }
             if (sk_tail) run_epilogue = sk_fast || sk_last;
-            const int sk_q0 = sk_fast ? 0 : -1, sk_q1 = (sk_tail && run_epilogue) ? sk_parts - 1 : -1;
+            const int sk_q0 = sk_fast ? 0 : -1, sk_q1 = (sk_tail && run_epilogue) ? tp.parts - 1 : -1;
 #pragma unroll 1
             for (int q = sk_q0; q < sk_q1; ++q) {
-                const float* src = slab0 + (long)(q < 0 ? sk_parts - 1 : q) * PW_SK_SLAB_FLOATS;
+                const float* src = slab0 + (long)(q < 0 ? tp.parts - 1 : q) * SK_PPW.slab_floats;
                 const bool replace = q < 0;                              // first slab of the re-read order REPLACES the accumulators
                 static_for<NFR>([&](auto gc_) {
                     constexpr int g = decltype(gc_)::value;
@@ -550,10 +509,10 @@ __global__ __launch_bounds__(512) void conv3x3_ppw_kernel(sp_conv_params p, int 
             ++it;
             cur = nxt;
             cur_is_tail = nxt_is_tail;
-            kc = cur_is_tail ? t_k0 : 0;
-            kc_end = cur_is_tail ? t_k1 : kchunks;
+            kc = cur_is_tail ? tp.k0 : 0;
+            kc_end = cur_is_tail ? tp.k1 : kchunks;
             nxt = item_coords(it + 1, nxt_is_tail);
-            bias_fetch(more_chunks && !(cur_is_tail && !t_owner), cur.co_i * CO_T);
+            bias_fetch(more_chunks && !(cur_is_tail && !tp.owner), cur.co_i * CO_T);
             acc_from_bias();
             stamp(5);
             if (half_b) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
@@ -582,11 +541,12 @@ int launch_ppw(const sp_conv_params& p, int prio, hipStream_t s) {
         attr_set = true;
     }
     const int cotiles = (p.cout + G::CO_T - 1) / G::CO_T;
-    const int total = p.n * (p.h / G::TH) * (p.w_ / G::TW) * cotiles;
+    const int total = (int)ppw_items(p.n, p.h, p.w_, p.cout);
     // persistent: one block per CU; the items of a last, partial round split along K where the caller lent the scratch
-    const PWSplit sk = pw_split_plan(total, (p.cin_p + G::KC - 1) / G::KC, (!TIMING && p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0);
+    const TailSplit sk = tail_split_plan(total, (p.cin_p + G::KC - 1) / G::KC, SK_PPW,
+                                         (!TIMING && p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0);
     sp_note_route("conv3x3_ppw<16bit> (64 co x 4 rows per wave)");
-    hipLaunchKernelGGL(kern, dim3((unsigned)sk.grid), dim3(512), G::LDS, s, p, cotiles, total, prio, sk.parts | (sp_tune(SP_TUNE_CONV_PP_SPLIT, 1) == 3 ? 256 : 0));
+    hipLaunchKernelGGL(kern, dim3((unsigned)sk.grid), dim3(512), G::LDS, s, p, cotiles, total, prio, tail_split_arg(sk));
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -596,30 +556,8 @@ int launch_ppw(const sp_conv_params& p, int prio, hipStream_t s) {
 // conv_igemm.hip's dispatch(): 16-bit 3x3 layers with more than 64 output channels on 16 x 32-pixel patches whose epilogue is the
 // FAST one.  Returns 1 if the shape is not covered (the caller then keeps its own kernel).
 int sp_conv_ppw_covers(const sp_conv_params& p) {
-    if (p.dtype != SP_BF16 || p.ksize != 3 || p.cout <= 64) return 0;
-    if (p.h % 16 != 0 || p.w_ % 32 != 0) return 0;
-    if ((long)p.n * p.h * p.w_ * p.cin_p * 2 >= (1L << 30) || (long)p.cout * 9 * p.cin_p * 2 >= (1L << 30)) return 0;
+    if (p.dtype != SP_BF16 || p.ksize != 3 || ppw_items(p.n, p.h, p.w_, p.cout) == 0 || !conv_operands_below_1g(p, 2)) return 0;
     return !((p.cout & 15) != 0 || (p.ldy & 7) != 0 || p.act == SP_ACT_TANH || p.tail_w != nullptr || p.pool_idx != nullptr || p.y == nullptr);
-}
-
-// sp_conv2d_workspace(): scratch for this kernel's K-split (0: it would not split / does not cover the dims)
-long sp_conv_ppw_split_workspace(int n, int h, int w, int cin_p, int cout) {
-    if (h % 16 != 0 || w % 32 != 0 || cout <= 64) return 0;
-    const long total = (long)n * (h / 16) * (w / 32) * ((cout + 127) / 128);
-    if (total >= (1L << 30)) return 0;
-    const PWSplit sk = pw_split_plan((int)total, (cin_p + 31) / 32, 1L << 40);
-    return (long)sk.tail_items * (sk.parts > 1 ? sk.parts : 0) * PW_SK_SLAB_FLOATS * 4;
-}
-
-// dispatch(): cost of `total` 16-row items in hundredths of ONE item's time on every CU (whole rounds without the split)
-long sp_conv_ppw_rounds100(long total, int cin_p, long workspace_bytes) {
-    const int kchunks = (cin_p + 31) / 32;
-    if (total < (1L << 30)) {
-        const PWSplit sk = pw_split_plan((int)total, kchunks, workspace_bytes);
-        if (sk.parts > 1 && total >= PW_NUM_CU)
-            return 100 * (total / PW_NUM_CU) + 100 * ((kchunks + sk.parts - 1) / sk.parts) / kchunks + 100 * (total >= 2 * PW_NUM_CU ? 60 : 90) * (sk.parts - 1) / (67 * kchunks) + 1;
-    }
-    return 100 * ((total + PW_NUM_CU - 1) / PW_NUM_CU);
 }
 
 int sp_conv_ppw_launch(const sp_conv_params& p, hipStream_t s) {

@@ -720,14 +720,15 @@ def packed_layer(module, training: bool, dtype, device) -> PackedLayer:
 # convolution / linear
 # ======================================================================================================
 # bench.py sets this to a list to time the convolution launches with events on the launch stream (eager steps only): entries
-# (start, end, algorithmic flops, family in {"fwd", "dgrad", "wgrad"}, is_dominant_kernel)
+# (start, end, algorithmic flops, family in {"fwd", "dgrad", "wgrad"}, None, route, shape, network) - the fifth slot is unused
+# (bench.py tells the dominant kernel by the route the library reports)
 KERNEL_PROBE = None
 # which network the probed launches belong to: "sn" = the spectral-normalised layers of G and D (the north-star's "3x3 spectral-norm
 # conv backward" is a sub-total over these), "vgg" while the frozen pyramid runs (models._VGGPyramidFn sets it)
 PROBE_NET = ["sn"]
 
 
-def _probed(family: str, flops: float, dominant: bool, fn, shape=None) -> None:
+def _probed(family: str, flops: float, fn, shape=None) -> None:
     """flops: EXECUTED multiply-adds x 2 of the launch on the layer's real channel counts (zero-padded channels - RGB 3 -> 8,
     513 -> 520 - are not work)."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -735,20 +736,7 @@ def _probed(family: str, flops: float, dominant: bool, fn, shape=None) -> None:
     fn()
     e1.record()
     route = L.lib().sp_last_route().decode()          # the kernel the entry point chose (include/sempyr.h: sp_last_route)
-    KERNEL_PROBE.append((e0, e1, flops, family, dominant, route, shape, PROBE_NET[0]))
-
-
-def _is_halo128(n, h, w, cout, ksize) -> bool:
-    """Launches that sp_conv2d_igemm routes to the 128 co x 8x32 px tile kernel (conv3x3_pp_kernel<bf16, 2>; with SP_CONV_PP=0
-    conv3x3_tall_kernel<.., 2, 8>; fp32: the latter): the kernel with the largest share of a step; mirrors dispatch() in
-    csrc/conv_igemm.hip, including the hand-over of some shapes to the 16-row tall kernel."""
-    if not (ksize == 3 and cout > 64 and h % 8 == 0 and w % 32 == 0):
-        return False
-    if h % 16 == 0:
-        bt = n * (h // 16) * (w // 32) * ((cout + 127) // 128)
-        if 19 * ((bt + 255) // 256) < 10 * ((2 * bt + 255) // 256):
-            return False
-    return True
+    KERNEL_PROBE.append((e0, e1, flops, family, None, route, shape, PROBE_NET[0]))
 
 
 TUNE_CONV_TALL, TUNE_IGEMM_DMA, TUNE_WGRAD_ROWS, TUNE_DETERMINISTIC = 0, 1, 2, 3
@@ -770,7 +758,7 @@ def conv_launch(x, w_ptr: int, bias, y, res1, res2, mask_src, slope: float, n, h
     """k_real: the layer's real reduction channels where cin_p counts zero padding (bench.py's FLOP bookkeeping only).
     pool_idx (with pool2 = 2): int32 tensor that receives the window positions of the maxima (include/sempyr.h)."""
     if KERNEL_PROBE is not None:
-        _probed(family, 2.0 * n * h * w * (k_real if k_real is not None else cin_p) * cout * ksize * ksize, _is_halo128(n, h, w, cout, ksize),
+        _probed(family, 2.0 * n * h * w * (k_real if k_real is not None else cin_p) * cout * ksize * ksize,
                 lambda: _conv_launch(x, w_ptr, bias, y, res1, res2, mask_src, slope, n, h, w, cin_p, cout, ldy, ksize, act, dtype, pool2, in_up2,
                                      img_scale, img_split, pool_idx),
                 (ksize, cin_p, cout, h, w, n))
@@ -1069,7 +1057,7 @@ class _ConvFn(torch.autograd.Function):
                 L.call("sp_conv2d_wgrad_accum_pair", ptr(x), ptr(dz), ptr(dwa), ptr(dba), ptr(dwb), ptr(dbb), ptr(ws), wsg, n, pair.split, h, w,
                        cin_p, cout, cout_p, ksize, 1 if up2 else 0, sp_dtype(dt), stream())
             if KERNEL_PROBE is not None:
-                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, False, launch_wgrad, (ksize, cin_p, cout, h, w, n))
+                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, launch_wgrad, (ksize, cin_p, cout, h, w, n))
             elif _wgrad_aside(h, w):
                 _on_wgrad_stream(launch_wgrad, [x, dz, ws])
             else:
@@ -1087,7 +1075,7 @@ class _ConvFn(torch.autograd.Function):
                 L.call("sp_conv2d_wgrad_accum_pooled" if up2 else "sp_conv2d_wgrad_accum", ptr(x), ptr(dz), ptr(dwsn), ptr(db), ptr(ws),
                        ws_floats, n, h, w, cin_p, cout, cout_p, ksize, sp_dtype(dt), stream())
             if KERNEL_PROBE is not None:
-                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, False, launch_wgrad, (ksize, cin_p, cout, h, w, n))
+                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, launch_wgrad, (ksize, cin_p, cout, h, w, n))
             elif _wgrad_aside(h, w) and pl.call.bank.direct_grads:
                 _on_wgrad_stream(launch_wgrad, [x, dz, ws])
             else:
@@ -1180,7 +1168,7 @@ def sn_conv2d_tail(x, m3, act3: int, m1, act1: int, keep_mid: bool = False):
     def launch():
         L.call("sp_conv2d_igemm", ctypes.byref(p), stream())
     if KERNEL_PROBE is not None:
-        _probed("fwd", 2.0 * n * h * w * 64 * (9 * pl3.cin + cout1), False, launch, (3, cin_p, 64, h, w, n))
+        _probed("fwd", 2.0 * n * h * w * 64 * (9 * pl3.cin + cout1), launch, (3, cin_p, 64, h, w, n))
     else:
         launch()
     return (mid, y) if keep_mid else y
@@ -1232,7 +1220,7 @@ class _ReusedLayerFn(torch.autograd.Function):
                 L.call("sp_conv2d_wgrad_accum", ptr(x), ptr(dy), ptr(dwsn), ptr(db), ptr(ws), ws_floats, n, h, w, cin_p, cout, cout_p, ksize,
                        sp_dtype(dt), stream())
             if KERNEL_PROBE is not None:
-                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, False, launch, (ksize, cin_p, cout, h, w, n))
+                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, launch, (ksize, cin_p, cout, h, w, n))
             else:
                 _launch_wgrad_deferring(launch, ws, defer_ok=db is None or pl.call.bank.direct_grads)
         else:
@@ -2050,6 +2038,6 @@ def conv_launch_f8(x8: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor, x_
     p.y8_inv_scale = y8_inv_scale.data_ptr() if y8_inv_scale is not None else None
     p.y8_amax = y8_amax.data_ptr() if y8_amax is not None else None
     if KERNEL_PROBE is not None:
-        _probed("fwd", 2.0 * n * h * w * cin_p * cout * 9, False, lambda: L.call("sp_conv2d_igemm", ctypes.byref(p), stream()), (3, cin_p, cout, h, w, n))
+        _probed("fwd", 2.0 * n * h * w * cin_p * cout * 9, lambda: L.call("sp_conv2d_igemm", ctypes.byref(p), stream()), (3, cin_p, cout, h, w, n))
         return
     L.call("sp_conv2d_igemm", ctypes.byref(p), stream())
