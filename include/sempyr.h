@@ -72,7 +72,9 @@ int sp_version(void);
  *                            generic kernels (default 1)
  *   SP_TUNE_CONV_PP          bf16 3x3 layers with Cout > 64: 0 = conv3x3_tall_kernel (round 2's lockstep schedule), 1 = the ping-pong
  *                            schedule of conv_pp.hip, tile height by round count (default), 8 / 16 = force that tile height
- *   SP_TUNE_WGRAD_PP         0 = the 3x3 weight gradient of wide maps stays on the 4-wave row walker (default 1: its ping-pong form)
+ *   SP_TUNE_WGRAD_PP         0 = the 3x3 weight gradient of wide maps stays on the 4-wave row walker (default 1: its ping-pong form),
+ *                            2 = like 1 (it used to select the alternating-row ping-pong kernel, which is gone), 3 = the cycle-stamp build of the
+ *                            ping-pong form (writes per-wave segment cycles into the scratch instead of a gradient)
  *   SP_TUNE_IGEMM_TILE       output tile of the LDS-DMA igemm on small-spatial 3x3 layers with Cout > 64: 0 = 64 co x 64 px, 1 = 128 x 128,
  *                            2 = 128 co x 64 px, 3 = 64 co x 128 px; default: 0, or 2 where 64 x 64 tiles make 1 - 2 rounds of the chip and K is long
  *   SP_TUNE_CONV_PPW         16-bit 3x3 layers with Cout > 64 on 16 x 32-pixel patches: the ping-pong kernel with 64 co x 4 rows per wave

@@ -549,10 +549,10 @@ int launch_attn_tq(bool fwd, const void* q, const void* k, const void* v, void* 
     const int lds_b = (NK * (D + 1) + TQ * D + TQ * DV + TQ * NK + TQ * 4 + 32 * (NK + 1)) * 4;
     dim3 grid(sp_div_up(N, TQ), B);
     if (fwd) {
-        { static int done = 0; if (done < lds_f) { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, TQ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_f); done = lds_f; } }
+        if (const int rc = sp_lds_limit<attn_fwd_kernel<T, TQ>>(lds_f)) return rc;
         hipLaunchKernelGGL((attn_fwd_kernel<T, TQ>), grid, dim3(256), lds_f, s, (const T*)q, (const T*)k, (const T*)v, (T*)o_or_dq, lse, N, NK, D, DV);
     } else {
-        { static int done = 0; if (done < lds_b) { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<T, TQ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); done = lds_b; } }
+        if (const int rc = sp_lds_limit<attn_bwd_kernel<T, TQ>>(lds_b)) return rc;
         hipLaunchKernelGGL((attn_bwd_kernel<T, TQ>), grid, dim3(256), lds_b, s, (const T*)q, (const T*)k, (const T*)v, (const T*)dout, lse,
                            (T*)o_or_dq, dk, dv, N, NK, D, DV);
     }
@@ -584,7 +584,7 @@ extern "C" int sp_attention_fwd(const void* q, const void* k, const void* v, voi
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == SP_BF16 && d % 32 == 0 && dv % 16 == 0 && dv <= 256 && nk % 32 == 0) {
         const int lds = nk * (dv * 2 + 32);
-        { static int done3 = 0; if (done3 < lds) { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); done3 = lds; } }
+        if (const int rc = sp_lds_limit<attn_fwd_mfma_kernel>(lds)) return rc;
         hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(sp_div_up(n, 64), batch), dim3(256), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                            (bf16*)o, lse, n, nk, d, dv);
         SP_LAUNCH_CHECK();
@@ -604,7 +604,7 @@ extern "C" int sp_attention_bwd(const void* q, const void* k, const void* v, con
     if (attn_bwd_mfma_ok(dtype, nk, d, dv)) {
         const int nqb = sp_div_up(n, AB_QB);           // one partial slab per query block (scratch: nqb x the gradient size)
         const int lds = nk * (d * 2 + 32) + AB_QB * (d * 2 + 32) + AB_QB * (dv * 2 + 32) + 2 * AB_QB * (nk * 2 + 32);
-        { static int done4 = 0; if (done4 < lds) { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); done4 = lds; } }
+        if (const int rc = sp_lds_limit<attn_bwd_mfma_kernel>(lds)) return rc;
         hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(nqb, batch), dim3(256), lds, s, (const bf16*)q, (const bf16*)k,
                            (const bf16*)v, (const bf16*)dout, lse, (bf16*)dq, dk_f32, dv_f32, n, nk, d, dv);
         hipLaunchKernelGGL(attn_reduce_kernel<bf16>, dim3(sp_div_up(nkd / 4, 256)), dim3(256), 0, s, dk_f32, nqb, nkd, (bf16*)dk);

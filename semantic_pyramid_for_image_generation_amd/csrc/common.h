@@ -138,6 +138,18 @@ extern "C" void sp_note_route(const char* name);
 #define SP_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { \
     sp_set_error("%s:%d HIP launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return SP_ERR_LAUNCH; } } while (0)
 
+// Before a launch with `bytes` of dynamic LDS: raises the kernel's limit (hipFuncAttributeMaxDynamicSharedMemorySize) the first time
+// it is launched with that much.  One high-water mark per kernel instantiation; SP_OK, or SP_ERR_LAUNCH with the error text set.
+template <auto KERNEL>
+static inline int sp_lds_limit(int bytes) {
+    static int granted = 0;
+    if (bytes <= granted) return SP_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", bytes, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
+    granted = bytes;
+    return SP_OK;
+}
+
 static inline int sp_div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
 // V elements (16 bytes when possible) per lane

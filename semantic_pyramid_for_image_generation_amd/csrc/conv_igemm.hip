@@ -442,13 +442,8 @@ __global__ __launch_bounds__(CO_T * 4) void conv3x3_halo_kernel(sp_conv_params p
 template <typename T, int CO_T, int TPS, bool IDX = false>
 int launch_halo(const sp_conv_params& p, hipStream_t s) {
     constexpr int LDS = HALO_PIX * 128 + 2 * TPS * CO_T * 128;
-    static bool attr_set = false;
-    auto kern = conv3x3_halo_kernel<T, CO_T, TPS, IDX>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv3x3_halo_kernel<T, CO_T, TPS, IDX>;
+    if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     dim3 grid((unsigned)(p.n * (p.h / HALO_TH) * (p.w_ / HALO_TW) * ((p.cout + CO_T - 1) / CO_T)));
     sp_note_route(sizeof(T) == 4 ? "conv3x3_halo<f32>" : "conv3x3_halo<16bit>");
     hipLaunchKernelGGL(kern, grid, dim3(CO_T * 4), LDS, s, p);
@@ -1034,13 +1029,8 @@ template <typename T, int WCO, int TH = 16, bool IDX = false>
 int launch_tall(const sp_conv_params& p, hipStream_t s) {
     constexpr int HP = WCO == 1 ? 36 : 40;
     constexpr int LDS = 2 * ((((TH + 2) * HP * 64 + 1023) / 1024) * 1024) + 2 * (WCO == 1 ? 9 : 3) * 64 * WCO * 64;
-    static bool attr_set = false;
-    auto kern = conv3x3_tall_kernel<T, WCO, TH, IDX>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv3x3_tall_kernel<T, WCO, TH, IDX>;
+    if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const int cotiles = (p.cout + 64 * WCO - 1) / (64 * WCO);
     const int total = p.n * (p.h / TH) * (p.w_ / TL_TW) * cotiles;
     int grid = total < g_num_cu ? total : g_num_cu;        // persistent: one block per CU
@@ -1083,13 +1073,8 @@ template <typename T, int WCO, int WPX, int FCO, int FPX>
 int launch_dma(const sp_conv_params& p, hipStream_t s) {
     constexpr int CO_T = WCO * FCO * 16, PX_T = WPX * FPX * 16;
     constexpr int LDS = 3 * (CO_T + PX_T) * 128;
-    static bool attr_set = false;
-    auto kern = conv_igemm_dma_kernel<T, WCO, WPX, FCO, FPX>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv_igemm_dma_kernel<T, WCO, WPX, FCO, FPX>;
+    if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const long M = (long)p.n * p.h * p.w_;
     const int tiles = (int)((M + PX_T - 1) / PX_T) * ((p.cout + CO_T - 1) / CO_T);
     const int e = p.dtype == SP_F32 ? 4 : 8;
@@ -1121,13 +1106,8 @@ template <typename T, int WCO, int WPX, int FCO, int FPX>
 int launch_cfg(const sp_conv_params& p, hipStream_t s) {
     constexpr int CO_T = WCO * FCO * 16, PX_T = WPX * FPX * 16;
     constexpr int LDS = 2 * (CO_T + PX_T) * 128;
-    static bool attr_set = false;
-    auto kern = conv_igemm_kernel<T, WCO, WPX, FCO, FPX>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv_igemm_kernel<T, WCO, WPX, FCO, FPX>;
+    if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const long M = (long)p.n * p.h * p.w_;
     dim3 grid((unsigned)((M + PX_T - 1) / PX_T), (unsigned)((p.cout + CO_T - 1) / CO_T));
     sp_note_route("conv_igemm (register-staged)");
@@ -1222,12 +1202,7 @@ int launch_1x1_direct(const sp_conv_params& p, hipStream_t s) {
     const int ksteps = (p.cin_p + 31) / 32;
     const int row_bytes = ((ksteps * 64 + 127) / 128) * 128 + 16;
     const int lds = 64 * row_bytes;
-    static int attr = 0;
-    if (attr < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_direct_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", lds, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr = lds;
-    }
+    if (const int rc = sp_lds_limit<conv1x1_direct_kernel>(lds)) return rc;
     const long M = (long)p.n * p.h * p.w_;
     const int cotiles = (p.cout + 63) / 64;
     long gx = (M + 127) / 128;                                           // one 32-pixel group per wave and pass at most
@@ -1527,12 +1502,7 @@ __global__ __launch_bounds__(256) void conv3x3_thinco_kernel(sp_conv_params p) {
 template <int KC>
 int launch_thinco(const sp_conv_params& p, hipStream_t s) {
     constexpr int LDS = TN_HH * TN_HW * (KC * 64 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_thinco_kernel<KC>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = sp_lds_limit<conv3x3_thinco_kernel<KC>>(LDS)) return rc;
     const long blocks = (long)p.n * (p.h / TN_TH) * (p.w_ / TN_TW);
     sp_note_route("conv3x3_thinco");
     hipLaunchKernelGGL(conv3x3_thinco_kernel<KC>, dim3((unsigned)blocks), dim3(256), LDS, s, p);

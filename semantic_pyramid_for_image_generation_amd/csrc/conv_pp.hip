@@ -772,13 +772,8 @@ int launch_pp(const sp_conv_params& p, int prio, hipStream_t s) {
     const int total = (int)items;
     constexpr int LDS_BYTES = TAIL ? G::LDS_TAIL : G::LDS;
     static_assert(LDS_BYTES <= 163840, "LDS budget");
-    static bool attr_set = false;
-    auto kern = conv3x3_pp_kernel<T, WCO, PRIO, TIMING, DMA_IN_L, FAST, FW, TAIL, IDX>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS_BYTES, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv3x3_pp_kernel<T, WCO, PRIO, TIMING, DMA_IN_L, FAST, FW, TAIL, IDX>;
+    if (const int rc = sp_lds_limit<kern>(LDS_BYTES)) return rc;
     const int cotiles = (p.cout + G::CO_T - 1) / G::CO_T;
     // persistent: one block per CU; the items of a last, partial round split along K where the caller lent the scratch (top of the file)
     const TailSplit sk = tail_split_plan(total, (p.cin_p + G::KC - 1) / G::KC, SK_PP,

@@ -533,13 +533,8 @@ template <typename T, bool TIMING, bool DMA_LB = true, bool POOL = false>
 int launch_ppw(const sp_conv_params& p, int prio, hipStream_t s) {
     using G = PWGeom<T>;
     static_assert(G::LDS <= 163840, "LDS budget");
-    static bool attr_set = false;
-    auto kern = conv3x3_ppw_kernel<T, TIMING, DMA_LB, POOL>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", G::LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv3x3_ppw_kernel<T, TIMING, DMA_LB, POOL>;
+    if (const int rc = sp_lds_limit<kern>(G::LDS)) return rc;
     const int cotiles = (p.cout + G::CO_T - 1) / G::CO_T;
     const int total = (int)ppw_items(p.n, p.h, p.w_, p.cout);
     // persistent: one block per CU; the items of a last, partial round split along K where the caller lent the scratch

@@ -616,13 +616,8 @@ int launch_wgrad9(const T* x, const T* dy, float* dw, int n, int h, int w, int c
                   const T* w_packed, float* dot, float* slabs, float* bias_slabs, int bias_ld, const WgPlan& pl, hipStream_t s) {
     constexpr int PXS = Wg9Traits<T>::PXS, PITCH = Wg9Traits<T>::PITCH;
     constexpr int LDS = (PXS + 3 * (PXS + 2)) * PITCH;
-    static bool attr_set = false;
-    auto kern = conv_wgrad9_kernel<T>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv_wgrad9_kernel<T>;
+    if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const long n_dw = (long)cout * 9 * cin;
     dim3 grid(sp_div_up(cin, 64), sp_div_up(cout, 64), (unsigned)pl.nsplit);
     sp_note_route("conv_wgrad9 (per-tap, <= 64 channels)");
@@ -638,13 +633,8 @@ int launch_wgrad(const T* x, const T* dy, float* dw, int n, int h, int w, int ci
                  hipStream_t s) {
     constexpr int CO_T = 2 * FCO * 16, CI_T = 2 * FCI * 16, PK = WgTraits<T>::PK;
     constexpr int LDS = 2 * PK * ((CO_T + CI_T) * (int)sizeof(T) + 2 * WgTraits<T>::PAD);
-    static bool attr_set = false;
-    auto kern = conv_wgrad_kernel<T, FCO, FCI>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
+    constexpr auto kern = conv_wgrad_kernel<T, FCO, FCI>;
+    if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const int taps = ksize * ksize;
     const long n_dw = (long)cout * taps * cin;
     dim3 grid(sp_div_up(cin, CI_T), sp_div_up(cout, CO_T), taps * pl.nsplit);

@@ -369,20 +369,10 @@ __global__ __launch_bounds__(256) void wgrad1x1_reduce_kernel(const float* __res
 
 struct W1Plan { int tiles, ci_tiles, nsplit, stages_per_split; bool ok; };
 
-W1Plan w1_plan(int n, int h, int w, int cin, int cout, int ld_dy) {
-    W1Plan p;
-    p.ok = false;
-    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
-    const long M = (long)n * h * w;
-    p.ci_tiles = (cin + 63) / 64;
-    p.tiles = p.ci_tiles * ((cout + 63) / 64);
-    p.nsplit = 1;
-    p.stages_per_split = 1;
-    if (target <= 0 || cin % 8 != 0 || ld_dy % 8 != 0) return p;
-    if (M * cin * 2 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31)) return p;           // 32-bit buffer offsets
+// the pixel split of a covered layer: ~target blocks (one per CU measured best: 128 / 192 / 256 / 384 / 512 -> 0.250 / 0.211 / 0.189 /
+// 0.201 / 0.197 ms over the step's fourteen shapes - more splits mean more slab traffic), at least four 64-pixel stages per split
+void w1_split(W1Plan& p, long M, int target) {
     const long stages = (M + 63) / 64;
-    // ~target blocks (one per CU measured best: 128 / 192 / 256 / 384 / 512 -> 0.250 / 0.211 / 0.189 / 0.201 / 0.197 ms over the step's
-    // fourteen shapes - more splits mean more slab traffic), at least four 64-pixel stages per split
     long nsplit = (target + p.tiles - 1) / p.tiles;
     if (nsplit > stages / 4) nsplit = stages / 4;
     if (nsplit < 1) nsplit = 1;
@@ -390,50 +380,50 @@ W1Plan w1_plan(int n, int h, int w, int cin, int cout, int ld_dy) {
     p.stages_per_split = (int)sps;
     p.nsplit = (int)((stages + sps - 1) / sps);
     p.ok = true;
+}
+
+W1Plan w1_plan(int n, int h, int w, int cin, int cout, int ld_dy) {
+    W1Plan p = {};
+    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
+    const long M = (long)n * h * w;
+    if (target <= 0 || cin % 8 != 0 || ld_dy % 8 != 0) return p;
+    if (M * cin * 2 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31)) return p;           // 32-bit buffer offsets
+    p.ci_tiles = (cin + 63) / 64;
+    p.tiles = p.ci_tiles * ((cout + 63) / 64);
+    w1_split(p, M, target);
     return p;
 }
 
-}  // namespace
-
-long sp_wgrad1x1_workspace(int n, int h, int w, int cin, int cout, int ld_dy) {
-    const W1Plan p = w1_plan(n, h, w, cin, cout, ld_dy);
-    if (!p.ok || p.nsplit <= 1) return 0;
-    return (long)p.nsplit * ((long)cout * cin + ((cout + 3) & ~3));
+// 3x3, 8-channel input (the padded RGB images): same contract, an im2col X tile of 72 columns
+W1Plan c8_plan(int n, int h, int w, int cout, int ld_dy) {
+    W1Plan p = {};
+    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
+    const long M = (long)n * h * w;
+    if (target <= 0 || (h & (h - 1)) != 0 || (w & (w - 1)) != 0 || ld_dy % 8 != 0) return p;
+    if (M * 16 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31) || M < 16384) return p;     // small maps: the row-walker is fine
+    p.ci_tiles = 1;
+    p.tiles = (cout + 63) / 64;
+    w1_split(p, M, target);
+    return p;
 }
 
-// SP_OK after launching, 1 if the layer is not covered (the caller falls back to the per-tap kernel)
-// Two reduce passes over the slab sub-ranges of the two groups of a two-group batch (sp_conv2d_wgrad_accum_pair): split k of the
-// streaming kernels covers the pixels [k, k + 1) * 64 * stages_per_split, so when the group boundary is a multiple of that every
-// slab belongs to one group.
-static void w1_reduce_groups(const W1Args& a, int nsplit, int kb, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int cout, hipStream_t s) {
+long w1_workspace(const W1Plan& p, long n_dw, int cout) { return (!p.ok || p.nsplit <= 1) ? 0 : (long)p.nsplit * (n_dw + ((cout + 3) & ~3)); }
+
+void w1_reduce(const W1Args& a, int k0, int k1, float* dw, float* dbias, hipStream_t s) {
+    const float* bias_slabs = a.bias_slabs != nullptr ? a.bias_slabs + (long)k0 * a.bias_ld : nullptr;
+    if (spq_push_reduce(a.slabs + (long)k0 * a.n_dw, k1 - k0, a.n_dw, dw, bias_slabs, a.bias_ld, a.COUT, dbias)) return;      // queued (reduce_queue.hip)
     const long cols = a.n_dw / 4 + (a.bias_slabs != nullptr ? a.bias_ld / 4 : 0);
-    for (int g = 0; g < 2; ++g) {
-        const int k0 = g ? kb : 0, k1 = g ? nsplit : kb;
-        if (spq_push_reduce(a.slabs + (long)k0 * a.n_dw, k1 - k0, a.n_dw, g ? dw_b : dw_a, a.bias_slabs != nullptr ? a.bias_slabs + (long)k0 * a.bias_ld : nullptr,
-                            a.bias_ld, cout, g ? dbias_b : dbias_a)) continue;          // queued (reduce_queue.hip)
-        hipLaunchKernelGGL(wgrad1x1_reduce_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, s, a.slabs + (long)k0 * a.n_dw, k1 - k0, a.n_dw,
-                           g ? dw_b : dw_a, a.bias_slabs != nullptr ? a.bias_slabs + (long)k0 * a.bias_ld : nullptr, a.bias_ld, cout, g ? dbias_b : dbias_a);
-    }
+    hipLaunchKernelGGL(wgrad1x1_reduce_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, s, a.slabs + (long)k0 * a.n_dw, k1 - k0, a.n_dw, dw,
+                       bias_slabs, a.bias_ld, a.COUT, dbias);
 }
 
-static int w1_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long split_pixels, int n, int h, int w,
-                          int cin, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s);
-
-int sp_wgrad1x1_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout, int ld_dy,
-                       float* ws, long ws_floats, hipStream_t s) {
-    return w1_launch_impl(x, dy, dw, dbias, nullptr, nullptr, 0, n, h, w, cin, cout, ld_dy, ws, ws_floats, s);
-}
-
-// the two-group form: 1 unless the layer runs with slabs and the group boundary falls between two splits
-int sp_wgrad1x1_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h, int w,
-                            int cin, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
-    if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
-    return w1_launch_impl(x, dy, dw_a, dbias_a, dw_b, dbias_b, (long)split * h * w, n, h, w, cin, cout, ld_dy, ws, ws_floats, s);
-}
-
-static int w1_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long split_pixels, int n, int h, int w,
-                          int cin, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
-    const W1Plan p = w1_plan(n, h, w, cin, cout, ld_dy);
+// Plan -> W1Args -> slab admission -> launch -> reduce, for both streaming kernels (EXTRA: what KERNEL takes after its W1Args) and both
+// entry points: one group (dw_b == nullptr), or the two groups of sp_conv2d_wgrad_accum_pair, whose pixels meet at split_pixels.  Split k
+// covers the pixels [k, k + 1) * 64 * stages_per_split, so when the group boundary is a multiple of that every slab belongs to one
+// group and each group gets its own reduce pass.  SP_OK after launching, 1 if the layer is not covered (the caller falls back).
+template <auto KERNEL, int LDS, typename... EXTRA>
+int w1_launch_impl(const W1Plan& p, const char* route, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b,
+                   long split_pixels, long M, int cin, int taps, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s, EXTRA... extra) {
     if (!p.ok) return 1;
     const long px_per_split = 64L * p.stages_per_split;
     if (dw_b != nullptr && (p.nsplit <= 1 || split_pixels % px_per_split != 0)) return 1;
@@ -442,8 +432,8 @@ static int w1_launch_impl(const void* x, const void* dy, float* dw, float* dbias
     a.dy = reinterpret_cast<const bf16*>(dy);
     a.dw = dw;
     a.dbias = dbias;
-    a.M = (long)n * h * w;
-    a.n_dw = (long)cout * cin;
+    a.M = M;
+    a.n_dw = (long)cout * taps * cin;
     a.CIN = cin; a.COUT = cout; a.LD_DY = ld_dy;
     a.ci_tiles = p.ci_tiles;
     a.tiles = p.tiles;
@@ -453,121 +443,62 @@ static int w1_launch_impl(const void* x, const void* dy, float* dw, float* dbias
     a.slabs = nullptr;
     a.bias_slabs = nullptr;
     if (p.nsplit > 1) {
-        if (ws == nullptr || ws_floats < (long)p.nsplit * (a.n_dw + a.bias_ld)) return 1;
+        if (ws == nullptr || ws_floats < w1_workspace(p, a.n_dw, cout)) return 1;
         a.slabs = ws;
         a.bias_slabs = dbias != nullptr ? ws + (long)p.nsplit * a.n_dw : nullptr;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W1_LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", W1_LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
-    sp_note_route(dw_b != nullptr ? "wgrad1x1_stream (two groups) + 2 x reduce" : "wgrad1x1_stream + reduce");
-    hipLaunchKernelGGL(wgrad1x1_stream_kernel, dim3((unsigned)(p.tiles * (p.nsplit >= 8 ? ((p.nsplit + 7) / 8) * 8 : p.nsplit))), dim3(256), W1_LDS, s, a);
+    if (const int rc = sp_lds_limit<KERNEL>(LDS)) return rc;
+    sp_note_route(route);
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(p.tiles * (p.nsplit >= 8 ? ((p.nsplit + 7) / 8) * 8 : p.nsplit))), dim3(256), LDS, s, a, extra...);
     SP_LAUNCH_CHECK();
     if (dw_b != nullptr) {
-        w1_reduce_groups(a, p.nsplit, (int)(split_pixels / px_per_split), dw, dbias, dw_b, dbias_b, cout, s);
-        SP_LAUNCH_CHECK();
-        return SP_OK;
+        const int kb = (int)(split_pixels / px_per_split);
+        w1_reduce(a, 0, kb, dw, dbias, s);
+        w1_reduce(a, kb, p.nsplit, dw_b, dbias_b, s);
+    } else if (p.nsplit > 1) {
+        w1_reduce(a, 0, p.nsplit, dw, dbias, s);
     }
-    if (p.nsplit > 1 && !spq_push_reduce(a.slabs, p.nsplit, a.n_dw, dw, a.bias_slabs, a.bias_ld, cout, dbias)) {
-        const long cols = a.n_dw / 4 + (a.bias_slabs != nullptr ? a.bias_ld / 4 : 0);
-        hipLaunchKernelGGL(wgrad1x1_reduce_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, s, a.slabs, p.nsplit, a.n_dw, dw, a.bias_slabs,
-                           a.bias_ld, cout, dbias);
-        SP_LAUNCH_CHECK();
-    }
+    SP_LAUNCH_CHECK();
     return SP_OK;
 }
 
-// ---- 3x3, 8-channel input (bf16): same contract
-static bool c8_plan(int n, int h, int w, int cout, int ld_dy, W1Plan& p) {
-    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
-    const long M = (long)n * h * w;
-    if (target <= 0 || (h & (h - 1)) != 0 || (w & (w - 1)) != 0 || ld_dy % 8 != 0) return false;
-    if (M * 16 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31) || M < 16384) return false;     // small maps: the row-walker is fine
-    p.ci_tiles = 1;
-    p.tiles = (cout + 63) / 64;
-    const long stages = (M + 63) / 64;
-    long nsplit = (target + p.tiles - 1) / p.tiles;
-    if (nsplit > stages / 4) nsplit = stages / 4;
-    if (nsplit < 1) nsplit = 1;
-    const long sps = (stages + nsplit - 1) / nsplit;
-    p.stages_per_split = (int)sps;
-    p.nsplit = (int)((stages + sps - 1) / sps);
-    p.ok = true;
-    return true;
+int c8_launch_impl(const char* route, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long split_pixels, int n, int h,
+                   int w, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
+    int logw = 0, logh = 0;
+    while ((1 << logw) < w) ++logw;
+    while ((1 << logh) < h) ++logh;
+    return w1_launch_impl<wgrad3x3_cin8_stream_kernel, C8_LDS>(c8_plan(n, h, w, cout, ld_dy), route, x, dy, dw, dbias, dw_b, dbias_b, split_pixels,
+                                                               (long)n * h * w, 8, 9, cout, ld_dy, ws, ws_floats, s, h, w, logw, logh);
 }
 
-long sp_wgrad3x3_cin8_workspace(int n, int h, int w, int cout, int ld_dy) {
-    W1Plan p;
-    if (!c8_plan(n, h, w, cout, ld_dy, p) || p.nsplit <= 1) return 0;
-    return (long)p.nsplit * ((long)cout * 72 + ((cout + 3) & ~3));
+}  // namespace
+
+long sp_wgrad1x1_workspace(int n, int h, int w, int cin, int cout, int ld_dy) { return w1_workspace(w1_plan(n, h, w, cin, cout, ld_dy), (long)cout * cin, cout); }
+
+int sp_wgrad1x1_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout, int ld_dy,
+                       float* ws, long ws_floats, hipStream_t s) {
+    return w1_launch_impl<wgrad1x1_stream_kernel, W1_LDS>(w1_plan(n, h, w, cin, cout, ld_dy), "wgrad1x1_stream + reduce", x, dy, dw, dbias, nullptr, nullptr, 0,
+                                                          (long)n * h * w, cin, 1, cout, ld_dy, ws, ws_floats, s);
 }
 
-static int c8_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long split_pixels, int n, int h, int w,
-                          int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s);
+// the two-group form: 1 unless the layer runs with slabs and the group boundary falls between two splits
+int sp_wgrad1x1_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h, int w,
+                            int cin, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
+    if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
+    return w1_launch_impl<wgrad1x1_stream_kernel, W1_LDS>(w1_plan(n, h, w, cin, cout, ld_dy), "wgrad1x1_stream (two groups) + 2 x reduce", x, dy, dw_a, dbias_a,
+                                                          dw_b, dbias_b, (long)split * h * w, (long)n * h * w, cin, 1, cout, ld_dy, ws, ws_floats, s);
+}
+
+long sp_wgrad3x3_cin8_workspace(int n, int h, int w, int cout, int ld_dy) { return w1_workspace(c8_plan(n, h, w, cout, ld_dy), (long)cout * 72, cout); }
 
 int sp_wgrad3x3_cin8_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cout, int ld_dy, float* ws,
                             long ws_floats, hipStream_t s) {
-    return c8_launch_impl(x, dy, dw, dbias, nullptr, nullptr, 0, n, h, w, cout, ld_dy, ws, ws_floats, s);
+    return c8_launch_impl("wgrad3x3_cin8_stream + reduce", x, dy, dw, dbias, nullptr, nullptr, 0, n, h, w, cout, ld_dy, ws, ws_floats, s);
 }
 
 int sp_wgrad3x3_cin8_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h,
                                  int w, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
     if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
-    return c8_launch_impl(x, dy, dw_a, dbias_a, dw_b, dbias_b, (long)split * h * w, n, h, w, cout, ld_dy, ws, ws_floats, s);
-}
-
-static int c8_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long split_pixels, int n, int h, int w,
-                          int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
-    W1Plan p;
-    if (!c8_plan(n, h, w, cout, ld_dy, p)) return 1;
-    const long px_per_split = 64L * p.stages_per_split;
-    if (dw_b != nullptr && (p.nsplit <= 1 || split_pixels % px_per_split != 0)) return 1;
-    W1Args a;
-    a.x = reinterpret_cast<const bf16*>(x);
-    a.dy = reinterpret_cast<const bf16*>(dy);
-    a.dw = dw;
-    a.dbias = dbias;
-    a.M = (long)n * h * w;
-    a.n_dw = (long)cout * 72;
-    a.CIN = 8; a.COUT = cout; a.LD_DY = ld_dy;
-    a.ci_tiles = 1;
-    a.tiles = p.tiles;
-    a.stages_per_split = p.stages_per_split;
-    a.nsplit = p.nsplit;
-    a.bias_ld = (cout + 3) & ~3;
-    a.slabs = nullptr;
-    a.bias_slabs = nullptr;
-    if (p.nsplit > 1) {
-        if (ws == nullptr || ws_floats < (long)p.nsplit * (a.n_dw + a.bias_ld)) return 1;
-        a.slabs = ws;
-        a.bias_slabs = dbias != nullptr ? ws + (long)p.nsplit * a.n_dw : nullptr;
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_cin8_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C8_LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", C8_LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        attr_set = true;
-    }
-    int logw = 0, logh = 0;
-    while ((1 << logw) < w) ++logw;
-    while ((1 << logh) < h) ++logh;
-    sp_note_route(dw_b != nullptr ? "wgrad3x3_cin8_stream (two groups) + 2 x reduce" : "wgrad3x3_cin8_stream + reduce");
-    hipLaunchKernelGGL(wgrad3x3_cin8_stream_kernel, dim3((unsigned)(p.tiles * (p.nsplit >= 8 ? ((p.nsplit + 7) / 8) * 8 : p.nsplit))), dim3(256), C8_LDS, s, a,
-                       h, w, logw, logh);
-    SP_LAUNCH_CHECK();
-    if (dw_b != nullptr) {
-        w1_reduce_groups(a, p.nsplit, (int)(split_pixels / px_per_split), dw, dbias, dw_b, dbias_b, cout, s);
-        SP_LAUNCH_CHECK();
-        return SP_OK;
-    }
-    if (p.nsplit > 1 && !spq_push_reduce(a.slabs, p.nsplit, a.n_dw, dw, a.bias_slabs, a.bias_ld, cout, dbias)) {
-        const long cols = a.n_dw / 4 + (a.bias_slabs != nullptr ? a.bias_ld / 4 : 0);
-        hipLaunchKernelGGL(wgrad1x1_reduce_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, s, a.slabs, p.nsplit, a.n_dw, dw, a.bias_slabs,
-                           a.bias_ld, cout, dbias);
-        SP_LAUNCH_CHECK();
-    }
-    return SP_OK;
+    return c8_launch_impl("wgrad3x3_cin8_stream (two groups) + 2 x reduce", x, dy, dw_a, dbias_a, dw_b, dbias_b, (long)split * h * w, n, h, w, cout, ld_dy, ws,
+                          ws_floats, s);
 }

@@ -30,6 +30,9 @@ constexpr int WR_YSLOT = 32 * 128;
 constexpr int WR_NSX = 10, WR_NSY = 6;
 constexpr int WR_XBYTES = WR_NSX * WR_XSLOT;
 constexpr int WR_LDS = WR_XBYTES + WR_NSY * WR_YSLOT;
+// the slab area in the caller's scratch: one partial tile [9 taps][64 co][64 ci] per block, then one partial bias row [64 co] per block
+constexpr int WR_MAX_SLABS = 512, WR_TILE_FLOATS = 9 * 64 * 64, WR_BIAS_FLOATS = 64;
+constexpr long WR_WS_FLOATS = (long)WR_MAX_SLABS * (WR_TILE_FLOATS + WR_BIAS_FLOATS);
 
 struct WrArgs {
     const bf16* x;
@@ -289,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_rows_kernel(WrArgs a) {
             }
             __syncthreads();
         }
-        float* slab = a.slabs != nullptr ? a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (9 * 64 * 64) : nullptr;
+        float* slab = a.slabs != nullptr ? a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * WR_TILE_FLOATS : nullptr;
         for (int e = tid; e < 9 * 64 * 16; e += 256) {
             const int row = e >> 4, c = e & 15;                    // row = tap * 64 + co (tile-local)
             const float v = tile[row * TPT + c] * oscale;
@@ -312,16 +315,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_rows_kernel(WrArgs a) {
             __syncthreads();
             if (tid < 64) {
                 const float v = (bsum[tid] + bsum[64 + tid] + bsum[128 + tid] + bsum[192 + tid]) * oscale;
-                if (a.bias_part != nullptr) a.bias_part[((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * 64 + tid] = v;
+                if (a.bias_part != nullptr) a.bias_part[((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * WR_BIAS_FLOATS + tid] = v;
                 else if (co0 + tid < a.COUT) atomicAdd(a.dbias + co0 + tid, v);
             }
         }
         return;
     }
-    // ---- merge: lane (ci = ci0 + wave*16 + i16, co = co0 + i*16 + g*4 + r)
+    // ---- merge: lane (ci = ci0 + wave*16 + i16, co = co0 + i*16 + g*4 + r); conv_wgrad_pp3_kernel ends with the twin of these statements
     if (a.slabs != nullptr) {
         // partial tile of this block, tile-local [tap][co][ci]; conv_wgrad_rows_reduce_kernel adds the slabs of a (co, ci) pair
-        float* slab = a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (9 * 64 * 64) + wave * 16 + i16;
+        float* slab = a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * WR_TILE_FLOATS + wave * 16 + i16;
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -342,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_rows_kernel(WrArgs a) {
                 }
     }
     if (do_bias && i16 == 0) {
-        float* bp = a.bias_part != nullptr ? a.bias_part + ((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * 64 : nullptr;
+        float* bp = a.bias_part != nullptr ? a.bias_part + ((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * WR_BIAS_FLOATS : nullptr;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -355,313 +358,28 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_rows_kernel(WrArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Ping-pong form of the row walker (round 3; wide maps, W % 32 == 0).  Same tile (64 co x 64 ci x 9 taps per block, a wave =
+// Ping-pong form of the row walker (wide maps, W % 32 == 0).  Same tile (64 co x 64 ci x 9 taps per block, a wave =
 // 64 co x 16 ci), same LDS image and transposed fragment reads as conv_wgrad_rows_kernel<0>, but
-//   * ONE block of 8 waves per CU instead of two of 4: the two waves of a SIMD hold the SAME dW tile and take alternate image
-//     rows, one segment apart (MI355X_MICROARCH.md, "Two waves per SIMD"): while one multiplies its row (36 + 4 MFMAs on
-//     registers only), its partner reads the 26 fragments of the next row and issues its share of the LDS-DMA;
-//   * a block walks a CONTIGUOUS range of image rows (flattened over image, strip, y), so the two halo rows are re-fetched only
-//     where a column starts; every step - halo or row - loads exactly one X row (+ one dY row) into ring slot `step mod 8`,
-//     every loading wave issues three requests per step (dummies where it has none), so all waits are `vmcnt(3)`;
+//   * ONE block of 8 waves per CU instead of two of 4: the two waves of a SIMD hold the SAME dW tile and run one segment apart
+//     (MI355X_MICROARCH.md, "Two waves per SIMD"): while one multiplies its row (36 + 4 MFMAs on registers only), its partner
+//     reads the fragments of its next row and issues its share of the LDS-DMA;
+//   * a block walks a CONTIGUOUS range of image rows (flattened over image, strip, y), each half of its waves its OWN contiguous
+//     half of it (own request cursor, own 4-slot ring), so the two halo rows are re-fetched only where a column starts; every
+//     step - halo or row - loads exactly one X row (+ one dY row) into ring slot `step mod 4`, every loading wave issues three
+//     requests per step (dummies where it has none), so all waits are the same counted `vmcnt`;
+//   * the X rows are carried in REGISTERS: two of the three X rows of a step are the previous step's, still in registers in
+//     fragment form, and a step reads only the row that is new - 8 + 6 transposed reads per 36 MFMAs (reading all three rows of
+//     every step from LDS, 8 + 18 reads, makes the LOAD segment longer than the MFMA segment it pairs with: ~830 against 576
+//     cycles).  Three register sets rotate their roles (tap row 0 / 1 / 2), so the step loop is unrolled by three with the set of
+//     every read and of every MFMA operand fixed at compile time, and the fragment halves are pinned to adjacent registers
+//     v180 .. v231 (A: 180-195, B sets: 196-231): with free allocation hipcc builds every MFMA operand tuple with two v_mov_b64
+//     (80 moves per 40 MFMAs inside the MFMA segment).  A ring slot is read in exactly one step (fragments of both operands), so
+//     a request distance of three steps needs four slots;
 //   * at the end the second half hands its accumulators to the first through LDS (the rings are dead by then) and ONE partial
 //     tile per block goes to the slab area: 256 slabs of 147 KB per layer instead of 512 (the merge was 16 % of the family's time).
 // ------------------------------------------------------------------------------------------------------------
-constexpr int WP_NS = 8, WP_D = 4;                           // ring slots (X and dY), request distance in steps
-constexpr int WP_XBYTES = WP_NS * WR_XSLOT, WP_YBYTES = WP_NS * WR_YSLOT;
-constexpr int WP_DUMMY = WP_XBYTES + WP_YBYTES;
-constexpr int WP_LDS = WP_DUMMY + 1024;                      // 74 752 B; the hand-over of 72 accumulator registers needs 73 728
+constexpr int WP_LDS = 8 * (WR_XSLOT + WR_YSLOT) + 1024;     // 74 752 B; the hand-over of 72 accumulator registers needs 73 728
 
-__global__ __launch_bounds__(512) void conv_wgrad_pp_kernel(WrArgs a, int rows_per_block, int rows_total) {
-    extern __shared__ __attribute__((aligned(16))) char wp_smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = wave >> 2, wq = wave & 3;
-    const int H = a.H, W = a.W, CIN = a.CIN;
-    const int co0 = (blockIdx.y / a.ci_tiles) * 64, ci0 = (blockIdx.y % a.ci_tiles) * 64;
-    const int strips = W / 32;
-    const int R0 = (int)blockIdx.x * rows_per_block;
-    const int R1 = R0 + rows_per_block < rows_total ? R0 + rows_per_block : rows_total;
-    if (R0 >= R1) return;
-    const int segs = (R1 - 1) / H - R0 / H + 1;            // columns touched: each starts with two halo steps
-    const int S = (R1 - R0) + 2 * segs;
-    const int S_pad = S + (S & 1);
-    const unsigned lds_base = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)wp_smem);
-    constexpr unsigned OOB = 0x80000000u;
-    auto uniform_ptr = [](const void* q) {
-        const unsigned long long v = (unsigned long long)(uintptr_t)q;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (void*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-    };
-    const int up = a.dy_up2 ? 1 : 0;
-    const int HY = H >> up, WY = W >> up;
-    const float oscale = up ? 0.25f : 1.f;
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.x), 0, __builtin_amdgcn_readfirstlane(a.N * H * W * CIN * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.dy), 0, __builtin_amdgcn_readfirstlane(a.N * HY * WY * a.LD_DY * 2), 0x00020000);
-
-    // ---- DMA lanes: pixel (lane >> 3) of an 8-pixel piece, logical 16-byte slot swizzled by (pixel >> 1) & 3 (see the kernel above)
-    const int dpx = lane >> 3;
-    const int dls = ((((lane & 7) >> 1) ^ ((dpx >> 1) & 3)) << 1) | (lane & 1);
-    const bool x_ch_ok = ci0 + dls * 8 < CIN;
-    const bool y_ch_ok = co0 + dls * 8 < a.LD_DY;
-    const unsigned x_lane = (unsigned)((ci0 + dls * 8) * 2), y_lane = (unsigned)((co0 + dls * 8) * 2);
-
-    // step cursor: (image n, strip origin x0, row y) of the step being REQUESTED; phase 0 / 1: halo steps (X rows y-1, y), phase 2: row
-    // step (X row y + 1, dY row y, the MFMAs of row y).  All incremental - an integer division costs ~50 scalar instructions, and
-    // a LOAD segment that spends them is longer than the partner's MFMA segment: the byte offsets of the column advance by one
-    // row pitch per row and are rebuilt only where a column starts.
-    struct Cursor { int n, x0, y, phase; unsigned xoff, yoff; };     // xoff: pixel (n, y, x0 - 1) of x; yoff: column origin of dy
-    const unsigned x_pitch = (unsigned)(W * CIN * 2), y_pitch = (unsigned)(WY * a.LD_DY * 2);
-    auto rebase = [&](Cursor& c) {
-        c.xoff = (unsigned)(((c.n * H + c.y) * W + c.x0 - 1) * CIN * 2);
-        c.yoff = (unsigned)(((c.n * HY) * WY + (c.x0 >> up)) * a.LD_DY * 2);
-    };
-    auto advance = [&](Cursor& c) {
-        if (c.phase < 2) { ++c.phase; return; }
-        c.xoff += x_pitch;
-        if (++c.y == H) {
-            c.y = 0; c.phase = 0;
-            c.x0 += 32;
-            if (c.x0 == W) { c.x0 = 0; ++c.n; }
-            rebase(c);
-        }
-    };
-    // per-lane constants of this wave's pieces: X piece wq (and piece 4 for wave 0), dY piece wq
-    const int px_a = wq * 8 + dpx, px_b = 32 + dpx;
-    const unsigned xl_a = (unsigned)(px_a * CIN * 2) + x_lane, xl_b = (unsigned)(px_b * CIN * 2) + x_lane;
-    const unsigned yl = (unsigned)((((wq * 8 + dpx) >> up) * a.LD_DY) * 2) + y_lane;
-    // the requests of step `c` (index s), issued by the four waves of the half that owns step s - D: X pieces 0..4 of one row
-    // (wave wq takes piece wq, wave 0 also piece 4), dY pieces 0..3 (wave wq takes piece wq); everything else is a dummy
-    auto issue_step = [&](const Cursor& c, int s) {
-        const bool live = s < S;
-        const int yx = c.y + c.phase - 1;
-        const bool xrow_ok = live && (unsigned)yx < (unsigned)H;
-        const unsigned xbase = c.xoff + (unsigned)(c.phase - 1) * x_pitch;
-        const unsigned slot_x = (unsigned)((s & (WP_NS - 1)) * WR_XSLOT), slot_y = (unsigned)(WP_XBYTES + (s & (WP_NS - 1)) * WR_YSLOT);
-        const bool left_edge = c.x0 == 0, right_edge = c.x0 + 32 == W;
-        {
-            const bool ok = xrow_ok && x_ch_ok && !(left_edge && px_a == 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (__attribute__((address_space(3))) void*)(wp_smem + slot_x + (unsigned)wq * 1024u),
-                                                     16, (int)(ok ? xbase + xl_a : OOB), 0, 0, 0);
-        }
-        {
-            const bool real = wq == 0;
-            const bool ok = real && xrow_ok && x_ch_ok && px_b < 34 && !(right_edge && px_b == 33);
-            const unsigned m = real ? 0xffffffffu : 0u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (__attribute__((address_space(3))) void*)(wp_smem + (((slot_x + 4096u) & m) | ((unsigned)WP_DUMMY & ~m))),
-                                                     16, (int)(ok ? xbase + xl_b : OOB), 0, 0, 0);
-        }
-        {
-            const bool real = live && c.phase == 2;
-            const unsigned off = (real && y_ch_ok) ? c.yoff + (unsigned)(c.y >> up) * y_pitch + yl : OOB;
-            const unsigned m = real ? 0xffffffffu : 0u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(y_rsrc, (__attribute__((address_space(3))) void*)(wp_smem + (((slot_y + (unsigned)wq * 1024u) & m) | ((unsigned)WP_DUMMY & ~m))),
-                                                     16, (int)off, 0, 0, 0);
-        }
-    };
-
-    // ---- fragment read offsets (the row walker's)
-    const int i16 = lane & 15, g = lane >> 4;
-    const int prow = g * 4 + (i16 >> 2);
-    unsigned a_off[4], b_off[3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a_off[i] = (unsigned)(prow * 128 + ((i ^ ((prow >> 1) & 3)) << 5) + (i16 & 3) * 8);
-#pragma unroll
-    for (int ds = 0; ds < 3; ++ds) b_off[ds] = (unsigned)((prow + ds) * 128 + ((wq ^ (((prow + ds) >> 1) & 3)) << 5) + (i16 & 3) * 8);
-
-    f32x4_t acc[9][4], accb[4];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) accb[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const bool do_bias = a.dbias != nullptr && ci0 == 0 && wq == 0;
-    const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, make_uint4(SP_H16_ONE_PAIR, SP_H16_ONE_PAIR, SP_H16_ONE_PAIR, SP_H16_ONE_PAIR));
-
-    // ---- prologue: steps 0 .. D-1 (each half requests the steps of its parity), everything landed before the first read.  Only
-    // the REQUEST cursor exists; whether the step being computed is a row step comes out of a two-entry history of its phases
-    Cursor rq;
-    {
-        const int col = R0 / H;
-        rq.y = R0 - col * H; rq.n = col / strips; rq.x0 = (col - rq.n * strips) * 32; rq.phase = 0;
-        rebase(rq);
-    }
-    if (half) advance(rq);
-    int ph_now = rq.phase;                                  // phase of the step this half computes next ...
-    issue_step(rq, half);
-    advance(rq); advance(rq);
-    int ph_next = rq.phase;                                 // ... and of the one after (requested 2 iterations = D steps ahead)
-    issue_step(rq, half + 2);
-    advance(rq); advance(rq);
-    wr_wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    if (half) __builtin_amdgcn_s_barrier();                 // this half runs one segment behind
-
-    for (int s = half; s < S_pad; s += 2) {
-        const bool compute = s < S && ph_now == 2;
-        ph_now = ph_next;
-        ph_next = rq.phase;                                 // the step requested in this iteration: s + D
-        // ================= LOAD segment =================
-        uint2 alo[4], ahi[4], blo[9], bhi[9];
-        const unsigned ab = lds_base + (unsigned)(WP_XBYTES + (s & (WP_NS - 1)) * WR_YSLOT);
-        unsigned bb[3];
-#pragma unroll
-        for (int dr = 0; dr < 3; ++dr) bb[dr] = lds_base + (unsigned)(((s - 2 + dr) & (WP_NS - 1)) * WR_XSLOT);
-        if (compute) {
-            // fragment halves pinned to adjacent registers v180 .. v231 (A: 180-195, B: 196-231): with free allocation hipcc builds every
-            // MFMA operand tuple with two v_mov_b64 (80 moves per 40 MFMAs inside the MFMA segment)
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[180:181]}"(alo[0]) : "v"(ab + a_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[182:183]}"(ahi[0]) : "v"(ab + a_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[184:185]}"(alo[1]) : "v"(ab + a_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[186:187]}"(ahi[1]) : "v"(ab + a_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[188:189]}"(alo[2]) : "v"(ab + a_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[190:191]}"(ahi[2]) : "v"(ab + a_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[192:193]}"(alo[3]) : "v"(ab + a_off[3]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[194:195]}"(ahi[3]) : "v"(ab + a_off[3]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[196:197]}"(blo[0]) : "v"(bb[0] + b_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[198:199]}"(bhi[0]) : "v"(bb[0] + b_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[200:201]}"(blo[1]) : "v"(bb[0] + b_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[202:203]}"(bhi[1]) : "v"(bb[0] + b_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[204:205]}"(blo[2]) : "v"(bb[0] + b_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[206:207]}"(bhi[2]) : "v"(bb[0] + b_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[208:209]}"(blo[3]) : "v"(bb[1] + b_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[210:211]}"(bhi[3]) : "v"(bb[1] + b_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[212:213]}"(blo[4]) : "v"(bb[1] + b_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[214:215]}"(bhi[4]) : "v"(bb[1] + b_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[216:217]}"(blo[5]) : "v"(bb[1] + b_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[218:219]}"(bhi[5]) : "v"(bb[1] + b_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[220:221]}"(blo[6]) : "v"(bb[2] + b_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[222:223]}"(bhi[6]) : "v"(bb[2] + b_off[0]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[224:225]}"(blo[7]) : "v"(bb[2] + b_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[226:227]}"(bhi[7]) : "v"(bb[2] + b_off[1]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[228:229]}"(blo[8]) : "v"(bb[2] + b_off[2]));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[230:231]}"(bhi[8]) : "v"(bb[2] + b_off[2]));
-        }
-        issue_step(rq, s + WP_D);
-        advance(rq); advance(rq);
-        wr_wait_vmcnt<3>();                                 // everything this wave requested before this segment has landed
-        wr_wait_lgkm<0>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // ================= MFMA segment =================
-        if (compute) {
-            __builtin_amdgcn_s_setprio(1);
-            wr_static_for<9>([&](auto tc) {
-                constexpr int t = decltype(tc)::value;
-                const bf16x8_t bf = wr_frag(blo[t], bhi[t]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr_frag(alo[i], ahi[i]), bf, acc[t][i], 0, 0, 0);
-            });
-            if (do_bias) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) accb[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr_frag(alo[i], ahi[i]), ones, accb[i], 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (!half) __builtin_amdgcn_s_barrier();               // the barrier the other half passes after its last segment
-
-    // ---- the second half's accumulators join the first half's through LDS (two passes of 72 registers + the bias sums)
-    wr_wait_vmcnt<0>();                                     // no request may land in the area any more
-    __syncthreads();
-    float* xch = reinterpret_cast<float*>(wp_smem);
-    const int ltid = tid & 255;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        if (half) {
-            int k = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (((t * 4 + i) & 1) == pass) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) xch[(k * 4 + r) * 256 + ltid] = acc[t][i][r];
-                        ++k;
-                    }
-                }
-        }
-        __syncthreads();
-        if (!half) {
-            int k = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (((t * 4 + i) & 1) == pass) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) acc[t][i][r] += xch[(k * 4 + r) * 256 + ltid];
-                        ++k;
-                    }
-                }
-        }
-        __syncthreads();
-    }
-    if (a.dbias != nullptr && ci0 == 0) {                   // ... and the bias sums (block-uniform condition)
-        if (half) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) xch[(i * 4 + r) * 256 + ltid] = accb[i][r];
-        }
-        __syncthreads();
-        if (!half) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) accb[i][r] += xch[(i * 4 + r) * 256 + ltid];
-        }
-    }
-    if (half) return;
-    // ---- merge of the block's tile: lane (ci = ci0 + wq*16 + i16, co = co0 + i*16 + g*4 + r), as the row walker
-    if (a.slabs != nullptr) {
-        float* slab = a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (9 * 64 * 64) + wq * 16 + i16;
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) slab[(t * 64 + i * 16 + g * 4 + r) * 64] = acc[t][i][r] * oscale;
-    }
-    const int ci = ci0 + wq * 16 + i16;
-    if (a.slabs == nullptr && ci < CIN) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = co0 + i * 16 + g * 4 + r;
-                    if (co < a.COUT) atomicAdd(a.dw + ((long)co * 9 + t) * CIN + ci, acc[t][i][r] * oscale);
-                }
-    }
-    if (do_bias && i16 == 0) {
-        float* bp = a.bias_part != nullptr ? a.bias_part + ((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * 64 : nullptr;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = i * 16 + g * 4 + r;
-                if (bp != nullptr) bp[col] = accb[i][r] * oscale;
-                else if (co0 + col < a.COUT) atomicAdd(a.dbias + co0 + col, accb[i][r] * oscale);
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// The same walk with the X rows carried in REGISTERS.  In the kernel above the halves take alternate row steps, so a wave
-// reads the fragments of all three X rows of its step from LDS: 8 + 18 transposed reads per 36 MFMAs - the LOAD segment
-// (~830 cycles of LDS pipe for four waves) is longer than the MFMA segment it pairs with (576).  Here each half walks its OWN
-// contiguous half of the block's row range (own request cursor, own 4-slot ring: the same LDS and the same L2 traffic): two of
-// the three X rows of a step are the previous step's, still in registers in fragment form, and a step reads only the row that is
-// new - 8 + 6 reads per 36 MFMAs.  Three register sets rotate their roles (tap row 0 / 1 / 2), so the step loop is unrolled by
-// three with the set of every read and of every MFMA operand fixed at compile time (sets pinned to v196.., as above).
-// A ring slot is read in exactly one step (fragments of both operands), so a request distance of three steps needs four slots.
-// ------------------------------------------------------------------------------------------------------------------------------
 #define WP3_BREAD(LO0, HI0, LO1, HI1, LO2, HI2, SET)                                                                               \
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "={v[" LO0 "]}"(Blo[SET][0]) : "v"(bbase + b_off[0]));                     \
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "={v[" HI0 "]}"(Bhi[SET][0]) : "v"(bbase + b_off[0]));                  \
@@ -944,8 +662,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_pp3_kernel(WrArgs a, int rows_
         }
     }
     if (half) return;
+    // ---- merge of the block's tile: the twin of conv_wgrad_rows_kernel's (a shared inline helper changes the code of both kernels)
     if (a.slabs != nullptr) {
-        float* slab = a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (9 * 64 * 64) + wq * 16 + i16;
+        float* slab = a.slabs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * WR_TILE_FLOATS + wq * 16 + i16;
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -966,7 +685,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_pp3_kernel(WrArgs a, int rows_
                 }
     }
     if (do_bias && i16 == 0) {
-        float* bp = a.bias_part != nullptr ? a.bias_part + ((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * 64 : nullptr;
+        float* bp = a.bias_part != nullptr ? a.bias_part + ((long)(blockIdx.y / a.ci_tiles) * gridDim.x + blockIdx.x) * WR_BIAS_FLOATS : nullptr;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -992,12 +711,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_reduce_kernel(const float
         // 64-thread groups of a block (a single chain over 512 partials took longer than the whole tile reduction)
         __shared__ float bred[256];
         const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
-        const float* bp = bias_part + (long)(blockIdx.y / ci_tiles) * nblk * 64 + col;
+        const float* bp = bias_part + (long)(blockIdx.y / ci_tiles) * nblk * WR_BIAS_FLOATS + col;
         float t = 0.f;
         // ordered: block 0 of the pair alone sums all partials (fixed order) and is the only writer of its dbias entries
         const int kstep = ordered ? 4 : gridDim.x * 4;
 #pragma unroll 8
-        for (int k = kbeg + (ordered ? 0 : blockIdx.x * 4) + grp; k < kend; k += kstep) t += bp[(long)k * 64];
+        for (int k = kbeg + (ordered ? 0 : blockIdx.x * 4) + grp; k < kend; k += kstep) t += bp[(long)k * WR_BIAS_FLOATS];
         bred[threadIdx.x] = t;
         __syncthreads();
         if (threadIdx.x < 64 && co0 + col < COUT) {
@@ -1005,16 +724,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_reduce_kernel(const float
             if (ordered) dbias[co0 + col] += tot; else atomicAdd(dbias + co0 + col, tot);
         }
     }
-    const float* base = slabs + (long)blockIdx.y * nblk * (9 * 64 * 64);
+    const float* base = slabs + (long)blockIdx.y * nblk * WR_TILE_FLOATS;
     const int e4 = blockIdx.x * 256 + threadIdx.x;                 // float4 index inside the tile: [tap][co][ci / 4]
     if (e4 >= 9 * 64 * 16) return;
     const int t = e4 / (64 * 16), co = co0 + (e4 / 16) % 64, ci = ci0 + (e4 % 16) * 4;
     if (co >= COUT || ci >= CIN || kbeg + (int)blockIdx.z >= kend) return;
-    float4 s = reinterpret_cast<const float4*>(base + (long)(kbeg + blockIdx.z) * (9 * 64 * 64))[e4];
+    float4 s = reinterpret_cast<const float4*>(base + (long)(kbeg + blockIdx.z) * WR_TILE_FLOATS)[e4];
     // (unrolled: the loads of eight slabs fly together - the plain loop waited for each: 17 us per launch for 75 MB)
 #pragma unroll 8
     for (int k = kbeg + blockIdx.z + gridDim.z; k < kend; k += gridDim.z) {
-        const float4 v = reinterpret_cast<const float4*>(base + (long)k * (9 * 64 * 64))[e4];
+        const float4 v = reinterpret_cast<const float4*>(base + (long)k * WR_TILE_FLOATS)[e4];
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     float* dst = dw + ((long)co * 9 + t) * CIN + ci;
@@ -1027,183 +746,182 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_reduce_kernel(const float
     }
 }
 
-}  // namespace
-
-// Returns SP_OK after launching, or 1 if the shape is not covered (caller falls back to the per-tap kernel).
 // narrow maps walk 2 (16 wide) or 4 (8 wide) images side by side.  16 x 16 maps gain (512 -> 512 at batch 20: 74.9 -> 49.7 us);
 // 8 x 8 maps have too few rows per block to amortise the pipeline ramp (24.0 -> 29.3 us) and stay on the per-tap kernel unless
 // SP_TUNE_WGRAD_ROWS = 3; 2 keeps every narrow map on the per-tap kernel
-static int wr_narrow(int h, int w, int dy_up2) {
+int wr_narrow(int h, int w, int dy_up2) {
     if (w % 32 == 0) return 0;
     const int mode = sp_tune(SP_TUNE_WGRAD_ROWS, 1);
     const bool covered = (w == 16 && mode != 2) || (w == 8 && mode == 3);
     return (covered && h % WR_R == 0 && !dy_up2) ? w : -1;
 }
 
-long sp_wgrad_rows_workspace(int n, int h, int w, int cin, int cout) {
-    if (wr_narrow(h, w, 0) < 0 || h % WR_R != 0) return 0;
-    return 512L * (9 * 64 * 64 + 64);          // partial tiles + partial bias sums of at most 512 blocks
-}
+enum WrForm { WR_ROWS_0, WR_ROWS_16, WR_ROWS_8, WR_PP3, WR_PP3_TIMING };
 
-int sp_wgrad_rows_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout,
-                         int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
+// What one launch does: filled by wr_plan from the dims, the scratch the caller lent and the tuning table (no HIP calls)
+struct WrPlan {
+    bool ok;                                 // false: not covered (the caller's other path takes the layer)
+    WrForm form;
+    int pairs, ci_tiles;                     // (co, ci) tile pairs = grid.y
+    int blocks;                              // blocks per pair = grid.x = slabs per pair
+    int rows_per_block, rows_total;          // ping-pong form: block b walks the flattened image rows [b, b + 1) * rows_per_block
+    int rows_per_unit, units, thin_mode;     // 4-wave form: block b takes the units b, b + blocks, ... (thin_mode: WrArgs)
+    bool slabs, bias_part;                   // partial tiles / bias rows go to the slab area + reduce pass (false: fp32 atomics)
+    bool ordered;                            // deterministic mode: one fixed-order chain per element in the reduce pass
+    int kb;                                  // two groups: the first block of the second group
+};
+
+// split: 0 = one group; otherwise the images [0, split) and [split, n) accumulate into different gradients (two groups)
+WrPlan wr_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, int dy_up2, bool have_dbias, long ws_floats) {
+    WrPlan p = {};
     const int nw = wr_narrow(h, w, dy_up2);
-    if (nw < 0 || h % WR_R != 0) return 1;
+    if (nw < 0 || h % WR_R != 0) return p;
+    if ((long)n * h * w * cin * 2 >= (1L << 30) || (long)n * h * w * ld_dy * 2 >= (1L << 30)) return p;
+    // wide maps: the ping-pong form (one 8-wave block per CU, contiguous row ranges, half the partial tiles) unless SP_TUNE_WGRAD_PP = 0
+    const int pp = nw == 0 ? sp_tune(SP_TUNE_WGRAD_PP, 1) : 0;
+    if (split > 0 && pp != 1 && pp != 2) return p;         // two groups: only where blocks walk contiguous rows
     const int strips = nw ? 1 : w / 32;                    // strips per image (wide maps) ...
     const int groups = nw ? (n + 32 / nw - 1) / (32 / nw) : n;   // ... or images per strip (narrow maps)
-    if ((long)n * h * w * cin * 2 >= (1L << 30) || (long)n * h * w * ld_dy * 2 >= (1L << 30)) return 1;
+    const int co_tiles = (cout + 63) / 64;
+    p.ci_tiles = (cin + 63) / 64;
+    p.pairs = co_tiles * p.ci_tiles;
+    p.ordered = sp_deterministic(SP_BF16);
+    const int env_slabs = p.ordered ? 1 : sp_tune(SP_TUNE_WGRAD_ROWS_SLABS, 1);         // 0: never, k > 1: one-group layers of at most k pairs
+    const bool slabs_ok = env_slabs && ws_floats >= WR_WS_FLOATS && cin % 4 == 0 && (env_slabs == 1 || (split == 0 && p.pairs <= env_slabs));
+    if (pp) {
+        p.form = pp == 3 ? WR_PP3_TIMING : WR_PP3;
+        p.thin_mode = pp == 3 ? sp_tune(SP_TUNE_WGRAD_ROWS_THIN, 0) : 0;               // (timing build: 8 / 9 leave out the requests / the dY reads)
+        p.rows_total = n * strips * h;
+        int nb = 256 / p.pairs;                            // one block per CU over all (co, ci) pairs of the layer
+        if (nb < 1) nb = 1;
+        p.rows_per_block = (p.rows_total + nb - 1) / nb;
+        if (p.rows_per_block < 8) p.rows_per_block = p.rows_total < 8 ? p.rows_total : 8;
+        p.blocks = (p.rows_total + p.rows_per_block - 1) / p.rows_per_block;
+    } else {
+        p.form = nw == 16 ? WR_ROWS_16 : nw == 8 ? WR_ROWS_8 : WR_ROWS_0;
+        p.thin_mode = sp_tune(SP_TUNE_WGRAD_ROWS_THIN, 1);
+        // Number of blocks: every block ends with one fp32-atomic merge of its 64 x 576 tile (measured ~0.17 us per block,
+        // serialised: all blocks of a (co, ci) pair hit the same addresses), so time ~ F / (T r) + T m with r ~ 2.4 TFLOP/s per
+        // block: T_opt = sqrt(F / (r m)) (scratch/bench_wgrad.py sweep, profiles/README.md), at most two blocks per CU.
+        // With slabs the merge is a plain 147 KB store per block + one reduce pass (no serialisation): fill the chip
+        const int env_blocks = sp_tune(SP_TUNE_WGRAD_ROWS_BLOCKS, 0);
+        const double flops = 2.0 * n * h * w * 9.0 * (64.0 * co_tiles) * (64.0 * p.ci_tiles);
+        int total = env_blocks > 0 ? env_blocks : (slabs_ok ? 512 : (int)(sqrt(flops * 2.45e-6) + 0.5));
+        if (total > 512) total = 512;
+        int target = (total + p.pairs / 2) / p.pairs;
+        if (target < 1) target = 1;
+        // units = (image, strip, row chunk of ru rows); block b takes units b, b + nblk, ...  Time ~ (units per block) x ru image rows,
+        // so ru and nblk are chosen to make every block walk the same number of rows: k = ceil(units / target) units each,
+        // nblk = ceil(units / k) blocks, cost k * ru - minimised over the power-of-two chunk heights down to 8 rows (a unit
+        // re-reads two halo rows, so ties go to the longer chunk).  The first version took the longest chunk that gave >= target
+        // units: 40 units on 32 blocks (256 -> 256 @64^2, batch 20) left 24 blocks idle half of the time (cost 128 instead of 80).
+        int ru = h, best_cost = 1 << 30, nblk = 1;
+        for (int r = h; r >= 8 || r == h; r /= 2) {
+            if (r % WR_R != 0) break;
+            const long units = (long)groups * strips * (h / r);
+            const long k = (units + target - 1) / target;
+            const long cost = k * (r + 1);                     // + 1: a mild preference for long chunks beyond exact ties
+            if (cost < best_cost) { best_cost = (int)cost; ru = r; nblk = (int)((units + k - 1) / k); }
+            if (r % 2 != 0 || r / 2 < 8) break;
+        }
+        // the deterministic mode needs every block's slab: fewer blocks where the area would not hold them
+        if (p.ordered && (long)nblk * p.pairs > WR_MAX_SLABS) nblk = WR_MAX_SLABS / p.pairs > 0 ? WR_MAX_SLABS / p.pairs : 1;
+        p.rows_per_unit = ru;
+        p.units = groups * strips * (h / ru);
+        p.blocks = nblk;
+    }
+    p.slabs = slabs_ok && (long)p.blocks * p.pairs <= WR_MAX_SLABS;
+    p.bias_part = p.slabs && have_dbias;
+    // deterministic mode never merges with atomics (the caller's ordered per-tap path takes the layer), and the two groups of a
+    // batch can only be told apart slab by slab, where their boundary falls between two blocks
+    if ((p.ordered || split > 0) && !p.slabs) return p;
+    if (split > 0) {
+        const long boundary = (long)split * strips * h;    // first flattened row of the second group
+        if (boundary % p.rows_per_block != 0) return p;
+        p.kb = (int)(boundary / p.rows_per_block);
+    }
+    p.ok = true;
+    return p;
+}
+
+// dW += the slabs [k0, k1) of every pair (all blocks, or the blocks that walked the rows of one group)
+void wr_reduce(const WrPlan& p, const WrArgs& a, int k0, int k1, float* dw, float* dbias, hipStream_t s) {
+    constexpr int TILE_BLOCKS = WR_TILE_FLOATS / 4 / 256;
+    int z = 512 / (TILE_BLOCKS * p.pairs);                 // ~512 reducer blocks
+    if (z > (k1 - k0) / 4) z = (k1 - k0) / 4;
+    if (z < 1 || p.ordered) z = 1;                         // deterministic mode: one ordered chain per element, no atomics
+    hipLaunchKernelGGL(conv_wgrad_rows_reduce_kernel, dim3(TILE_BLOCKS, (unsigned)p.pairs, (unsigned)z), dim3(256), 0, s, a.slabs, p.blocks, dw, a.CIN,
+                       a.COUT, a.ci_tiles, a.bias_part, dbias, p.ordered ? 1 : 0, k0, k1);
+}
+
+template <auto KERNEL, typename... EXTRA>
+int wr_launch_kernel(const char* route, const WrPlan& p, int threads, int lds, hipStream_t s, const WrArgs& a, EXTRA... extra) {
+    if (const int rc = sp_lds_limit<KERNEL>(lds)) return rc;
+    sp_note_route(route);
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)p.blocks, (unsigned)p.pairs), dim3(threads), lds, s, a, extra...);
+    return SP_OK;
+}
+
+// Plan -> WrArgs -> launch -> reduce pass(es), for one group (dw_b == nullptr, split == 0) and for two: ONE launch of the ping-pong
+// form over all n images (a block walks a contiguous range of image rows, so when the group boundary falls between two blocks every
+// partial tile belongs to one group) and one reduce pass per group over that group's slabs.
+// SP_OK after launching, 1 if the shape / plan is not covered.
+int wr_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int split, int h, int w, int cin,
+                   int cout, int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
+    const WrPlan p = wr_plan(n, split, h, w, cin, cout, ld_dy, dy_up2, dbias != nullptr, ws != nullptr ? ws_floats : 0);
+    if (!p.ok) return 1;
     WrArgs a;
     a.x = reinterpret_cast<const bf16*>(x);
     a.dy = reinterpret_cast<const bf16*>(dy);
     a.dw = dw;
-    a.dbias = dbias;
+    a.dbias = dbias;                                       // (with slabs: only its being non-null matters)
+    a.slabs = p.slabs ? ws : nullptr;
+    a.bias_part = p.bias_part ? ws + (long)WR_MAX_SLABS * WR_TILE_FLOATS : nullptr;
     a.N = n; a.H = h; a.W = w; a.CIN = cin; a.COUT = cout; a.LD_DY = ld_dy;
+    a.rows_per_unit = p.rows_per_unit;
+    a.units = p.units;
+    a.ci_tiles = p.ci_tiles;
+    a.thin_mode = p.thin_mode;
     a.dy_up2 = dy_up2;
-    a.thin_mode = sp_tune(SP_TUNE_WGRAD_ROWS_THIN, 1);
-    const int co_tiles = (cout + 63) / 64;
-    a.ci_tiles = (cin + 63) / 64;
-    const int pairs = co_tiles * a.ci_tiles;
-    // Number of blocks: every block ends with one fp32-atomic merge of its 64 x 576 tile (measured ~0.17 us per block,
-    // serialised: all blocks of a (co, ci) pair hit the same addresses), so time ~ F / (T r) + T m with r ~ 2.4 TFLOP/s per
-    // block: T_opt = sqrt(F / (r m)) (scratch/bench_wgrad.py sweep, profiles/README.md), at most two blocks per CU.
-    const int env_blocks = sp_tune(SP_TUNE_WGRAD_ROWS_BLOCKS, 0);
-    const bool det = sp_deterministic(SP_BF16);
-    const int env_slabs = det ? 1 : sp_tune(SP_TUNE_WGRAD_ROWS_SLABS, 1);
-    const bool use_slabs = env_slabs && ws != nullptr && ws_floats >= 512L * (9 * 64 * 64 + 64) && cin % 4 == 0 && (env_slabs == 1 || pairs <= env_slabs);
-    if (det && !use_slabs) return 1;                       // deterministic mode never merges with atomics: the caller's ordered per-tap path takes the layer
-    const double flops = 2.0 * n * h * w * 9.0 * (64.0 * co_tiles) * (64.0 * a.ci_tiles);
-    // with slabs the merge is a plain 147 KB store per block + one reduce pass (no serialisation): fill the chip
-    int total = env_blocks > 0 ? env_blocks : (use_slabs ? 512 : (int)(sqrt(flops * 2.45e-6) + 0.5));
-    if (total > 512) total = 512;
-    int target = (total + pairs / 2) / pairs;
-    if (target < 1) target = 1;
-    // units = (image, strip, row chunk of ru rows); block b takes units b, b + nblk, ...  Time ~ (units per block) x ru image rows,
-    // so ru and nblk are chosen to make every block walk the same number of rows: k = ceil(units / target) units each,
-    // nblk = ceil(units / k) blocks, cost k * ru - minimised over the power-of-two chunk heights down to 8 rows (a unit
-    // re-reads two halo rows, so ties go to the longer chunk).  The first version took the longest chunk that gave >= target
-    // units: 40 units on 32 blocks (256 -> 256 @64^2, batch 20) left 24 blocks idle half of the time (cost 128 instead of 80).
-    int ru = h, best_cost = 1 << 30, nblk = 1;
-    for (int r = h; r >= 8 || r == h; r /= 2) {
-        if (r % WR_R != 0) break;
-        const long units = (long)groups * strips * (h / r);
-        const long k = (units + target - 1) / target;
-        const long cost = k * (r + 1);                     // + 1: a mild preference for long chunks beyond exact ties
-        if (cost < best_cost) { best_cost = (int)cost; ru = r; nblk = (int)((units + k - 1) / k); }
-        if (r % 2 != 0 || r / 2 < 8) break;
+    const char* pp3_route = dw_b != nullptr ? "conv_wgrad_pp3 (row walker, ping-pong, two groups) + 2 x rows_reduce"
+                                            : "conv_wgrad_pp3 (row walker, ping-pong) + rows_reduce";
+    int rc = SP_OK;
+    switch (p.form) {
+        case WR_ROWS_0: rc = wr_launch_kernel<conv_wgrad_rows_kernel<0>>("conv_wgrad_rows<0> + rows_reduce", p, 256, WR_LDS, s, a); break;
+        case WR_ROWS_16: rc = wr_launch_kernel<conv_wgrad_rows_kernel<16>>("conv_wgrad_rows<16> + rows_reduce", p, 256, WR_LDS, s, a); break;
+        case WR_ROWS_8: rc = wr_launch_kernel<conv_wgrad_rows_kernel<8>>("conv_wgrad_rows<8> + rows_reduce", p, 256, WR_LDS, s, a); break;
+        case WR_PP3: rc = wr_launch_kernel<conv_wgrad_pp3_kernel<false>>(pp3_route, p, 512, WP3_LDS, s, a, p.rows_per_block, p.rows_total); break;
+        case WR_PP3_TIMING: rc = wr_launch_kernel<conv_wgrad_pp3_kernel<true>>(pp3_route, p, 512, WP3_LDS, s, a, p.rows_per_block, p.rows_total); break;
     }
-    a.rows_per_unit = ru;
-    a.units = groups * strips * (h / ru);
-    // wide maps: the ping-pong form (one 8-wave block per CU, contiguous row ranges, half the partial tiles)
-    if (nw == 0 && sp_tune(SP_TUNE_WGRAD_PP, 1)) {
-        const int rows_total = n * strips * h;
-        int nb = 256 / pairs;                                // one block per CU over all (co, ci) pairs of the layer
-        if (nb < 1) nb = 1;
-        int rpb = (rows_total + nb - 1) / nb;
-        if (rpb < 8) rpb = rows_total < 8 ? rows_total : 8;
-        nb = (rows_total + rpb - 1) / rpb;
-        static bool pp_attr = false;
-        if (!pp_attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_pp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_pp3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, WP3_LDS);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_pp3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, WP3_LDS);
-            if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", WP_LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-            pp_attr = true;
-        }
-        a.slabs = use_slabs && (long)nb * pairs <= 512 ? ws : nullptr;
-        a.bias_part = (a.slabs != nullptr && dbias != nullptr) ? ws + 512L * 9 * 64 * 64 : nullptr;
-        a.thin_mode = 0;
-        sp_note_route("conv_wgrad_pp3 (row walker, ping-pong) + rows_reduce");
-        if (sp_tune(SP_TUNE_WGRAD_PP, 1) == 2) hipLaunchKernelGGL(conv_wgrad_pp_kernel, dim3((unsigned)nb, (unsigned)pairs), dim3(512), WP_LDS, s, a, rpb, rows_total);
-        else if (sp_tune(SP_TUNE_WGRAD_PP, 1) == 3) { a.thin_mode = sp_tune(SP_TUNE_WGRAD_ROWS_THIN, 0); hipLaunchKernelGGL(conv_wgrad_pp3_kernel<true>, dim3((unsigned)nb, (unsigned)pairs), dim3(512), WP3_LDS, s, a, rpb, rows_total); SP_LAUNCH_CHECK(); return SP_OK; }
-        else hipLaunchKernelGGL(conv_wgrad_pp3_kernel<false>, dim3((unsigned)nb, (unsigned)pairs), dim3(512), WP3_LDS, s, a, rpb, rows_total);
-        if (a.slabs != nullptr) {
-            int z = 512 / (36 * pairs);
-            if (z > nb / 4) z = nb / 4;
-            if (z < 1 || det) z = 1;
-            hipLaunchKernelGGL(conv_wgrad_rows_reduce_kernel, dim3(9 * 64 * 16 / 256, (unsigned)pairs, (unsigned)z), dim3(256), 0, s, ws, nb, dw, cin, cout, a.ci_tiles, a.bias_part, dbias, det ? 1 : 0, 0, nb);
-        }
-        SP_LAUNCH_CHECK();
-        return SP_OK;
-    }
-    // the slab area holds 512 partial tiles; the deterministic mode must not fall back to atomics with several blocks per pair
-    if (det && (long)nblk * pairs > 512) nblk = 512 / pairs > 0 ? 512 / pairs : 1;
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (const void* k : {reinterpret_cast<const void*>(conv_wgrad_rows_kernel<0>), reinterpret_cast<const void*>(conv_wgrad_rows_kernel<16>),
-                              reinterpret_cast<const void*>(conv_wgrad_rows_kernel<8>)}) {
-            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, WR_LDS);
-            if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", WR_LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        }
-        attr_set = true;
-    }
-    a.slabs = use_slabs && (long)nblk * pairs <= 512 ? ws : nullptr;
-    a.bias_part = (a.slabs != nullptr && dbias != nullptr) ? ws + 512L * 9 * 64 * 64 : nullptr;
-    sp_note_route(nw == 16 ? "conv_wgrad_rows<16> + rows_reduce" : nw == 8 ? "conv_wgrad_rows<8> + rows_reduce" : "conv_wgrad_rows<0> + rows_reduce");
-    if (nw == 16) hipLaunchKernelGGL(conv_wgrad_rows_kernel<16>, dim3((unsigned)nblk, (unsigned)pairs), dim3(256), WR_LDS, s, a);
-    else if (nw == 8) hipLaunchKernelGGL(conv_wgrad_rows_kernel<8>, dim3((unsigned)nblk, (unsigned)pairs), dim3(256), WR_LDS, s, a);
-    else hipLaunchKernelGGL(conv_wgrad_rows_kernel<0>, dim3((unsigned)nblk, (unsigned)pairs), dim3(256), WR_LDS, s, a);
-    if (a.slabs != nullptr) {
-        int z = 512 / (36 * pairs);                       // ~512 reducer blocks
-        if (z > nblk / 4) z = nblk / 4;
-        if (z < 1 || det) z = 1;                          // deterministic mode: one ordered chain per element, no atomics
-        hipLaunchKernelGGL(conv_wgrad_rows_reduce_kernel, dim3(9 * 64 * 16 / 256, (unsigned)pairs, (unsigned)z), dim3(256), 0, s, ws, nblk, dw, cin, cout, a.ci_tiles, a.bias_part, dbias, det ? 1 : 0, 0, nblk);
+    if (rc != SP_OK) return rc;
+    if (p.form == WR_PP3_TIMING) {
+        // cycle counts in the slab area instead of a gradient: nothing to reduce
+    } else if (dw_b != nullptr) {
+        wr_reduce(p, a, 0, p.kb, dw, dbias, s);
+        wr_reduce(p, a, p.kb, p.blocks, dw_b, dbias_b, s);
+    } else if (p.slabs) {
+        wr_reduce(p, a, 0, p.blocks, dw, dbias, s);
     }
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
 
-// Two-group batch (sp_conv2d_wgrad_accum_pair): images [0, split) accumulate into (dw_a, dbias_a), the rest into (dw_b, dbias_b) -
-// ONE launch of the ping-pong row walker over all n images (a block walks a contiguous range of image rows, so when the group
-// boundary falls between two blocks every partial tile belongs to one group) and one reduce pass per group over that group's
-// slabs.  Returns SP_OK after launching, 1 if the shape / plan is not covered (the caller then runs the two groups separately).
+}  // namespace
+
+// partial tiles + partial bias sums of at most WR_MAX_SLABS blocks, for every shape a form covers
+long sp_wgrad_rows_workspace(int n, int h, int w, int cin, int cout) {
+    return (wr_narrow(h, w, 0) < 0 || h % WR_R != 0) ? 0 : WR_WS_FLOATS;
+}
+
+int sp_wgrad_rows_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout,
+                         int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
+    return wr_launch_impl(x, dy, dw, dbias, nullptr, nullptr, n, 0, h, w, cin, cout, ld_dy, ws, ws_floats, dy_up2, s);
+}
+
+// Two-group batch (sp_conv2d_wgrad_accum_pair): images [0, split) accumulate into (dw_a, dbias_a), the rest into (dw_b, dbias_b);
+// 1 where that takes two launches (the caller then runs the two groups separately)
 int sp_wgrad_rows_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split,
                               int h, int w, int cin, int cout, int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
-    if (wr_narrow(h, w, dy_up2) != 0 || h % WR_R != 0 || sp_tune(SP_TUNE_WGRAD_PP, 1) != 1 || split <= 0 || split >= n) return 1;
-    if ((dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
-    if ((long)n * h * w * cin * 2 >= (1L << 30) || (long)n * h * w * ld_dy * 2 >= (1L << 30)) return 1;
-    const bool det = sp_deterministic(SP_BF16);
-    const int env_slabs = det ? 1 : sp_tune(SP_TUNE_WGRAD_ROWS_SLABS, 1);
-    const int co_tiles = (cout + 63) / 64, ci_tiles = (cin + 63) / 64, pairs = co_tiles * ci_tiles;
-    if (!(env_slabs == 1 && ws != nullptr && ws_floats >= 512L * (9 * 64 * 64 + 64) && cin % 4 == 0)) return 1;
-    const int strips = w / 32;
-    const int rows_total = n * strips * h;
-    int nb = 256 / pairs;
-    if (nb < 1) nb = 1;
-    int rpb = (rows_total + nb - 1) / nb;
-    if (rpb < 8) rpb = rows_total < 8 ? rows_total : 8;
-    nb = (rows_total + rpb - 1) / rpb;
-    const long boundary = (long)split * strips * h;                     // first flattened row of the second group
-    if (boundary % rpb != 0 || (long)nb * pairs > 512) return 1;
-    const int kb = (int)(boundary / rpb);
-    WrArgs a;
-    a.x = reinterpret_cast<const bf16*>(x);
-    a.dy = reinterpret_cast<const bf16*>(dy);
-    a.dw = dw_a;
-    a.dbias = dbias_a;                                                   // (with slabs: only its being non-null matters)
-    a.N = n; a.H = h; a.W = w; a.CIN = cin; a.COUT = cout; a.LD_DY = ld_dy;
-    a.dy_up2 = dy_up2;
-    a.thin_mode = 0;
-    a.ci_tiles = ci_tiles;
-    a.rows_per_unit = h;
-    a.units = n * strips;
-    a.slabs = ws;
-    a.bias_part = dbias_a != nullptr ? ws + 512L * 9 * 64 * 64 : nullptr;
-    static bool pp_attr = false;
-    if (!pp_attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_pp3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, WP3_LDS);
-        if (e != hipSuccess) { sp_set_error("hipFuncSetAttribute(LDS=%d) failed: %s", WP3_LDS, hipGetErrorString(e)); return SP_ERR_LAUNCH; }
-        pp_attr = true;
-    }
-    sp_note_route("conv_wgrad_pp3 (row walker, ping-pong, two groups) + 2 x rows_reduce");
-    hipLaunchKernelGGL(conv_wgrad_pp3_kernel<false>, dim3((unsigned)nb, (unsigned)pairs), dim3(512), WP3_LDS, s, a, rpb, rows_total);
-    for (int grp = 0; grp < 2; ++grp) {
-        const int k0 = grp ? kb : 0, k1 = grp ? nb : kb;
-        int z = 512 / (36 * pairs);
-        if (z > (k1 - k0) / 4) z = (k1 - k0) / 4;
-        if (z < 1 || det) z = 1;
-        hipLaunchKernelGGL(conv_wgrad_rows_reduce_kernel, dim3(9 * 64 * 16 / 256, (unsigned)pairs, (unsigned)z), dim3(256), 0, s, ws, nb, grp ? dw_b : dw_a,
-                           cin, cout, ci_tiles, a.bias_part, grp ? dbias_b : dbias_a, det ? 1 : 0, k0, k1);
-    }
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
+    return wr_launch_impl(x, dy, dw_a, dbias_a, dw_b, dbias_b, n, split, h, w, cin, cout, ld_dy, ws, ws_floats, dy_up2, s);
 }

@@ -322,9 +322,8 @@ static inline bool linear_use_mfma(int dtype, int batch, int k, int n) { return 
 template <int KS, int NB>
 static void launch_linear_mfma_nb(dim3 grid, hipStream_t s, const bf16* x, int ldx, const bf16* w, int kp, float* scratch, int batch, int k, int n,
                                   const LinTail& tail) {
-    static bool a = false;
     const int lds = 16 * NB * ((KS < 512 ? KS : 512) * 2 + 16);
-    if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear_mfma_kernel<KS, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); a = true; }
+    (void)sp_lds_limit<linear_mfma_kernel<KS, NB>>(lds);          // (a refusal shows as the launch error the caller checks for)
     hipLaunchKernelGGL((linear_mfma_kernel<KS, NB>), grid, dim3(256), lds, s, x, ldx, w, kp, scratch, batch, k, n, tail);
 }
 
@@ -346,13 +345,11 @@ extern "C" int sp_linear_fwd(const void* x, int32_t ldx, const void* w_packed, i
     dim3 grid(sp_div_up(n, LIN_NB), sp_div_up(batch, LIN_BMAX));
     const int lds = LIN_BMAX * LIN_PITCH * sizeof(float);
     if (dtype == SP_F32) {
-        static bool a = false;
-        if (!a) { hipFuncSetAttribute(reinterpret_cast<const void*>(linear_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); a = true; }
+        if (const int rc = sp_lds_limit<linear_fwd_kernel<float>>(lds)) return rc;
         hipLaunchKernelGGL(linear_fwd_kernel<float>, grid, dim3(256), lds, s, (const float*)x, ldx, (const float*)w_packed, kp, bias,
                            (const float*)res, (float*)y, ldy, batch, k, n, act);
     } else {
-        static bool a = false;
-        if (!a) { hipFuncSetAttribute(reinterpret_cast<const void*>(linear_fwd_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); a = true; }
+        if (const int rc = sp_lds_limit<linear_fwd_kernel<bf16>>(lds)) return rc;
         hipLaunchKernelGGL(linear_fwd_kernel<bf16>, grid, dim3(256), lds, s, (const bf16*)x, ldx, (const bf16*)w_packed, kp, bias,
                            (const bf16*)res, (bf16*)y, ldy, batch, k, n, act);
     }
