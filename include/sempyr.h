@@ -186,6 +186,9 @@ int sp_conv2d_igemm(const sp_conv_params* p, sp_stream_t stream);
  * holds one partial [n*h*w][cout] slab per split; it needs no initialisation and carries nothing between calls. */
 int sp_conv2d_workspace(int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ksize, int32_t dtype,
                         int64_t* bytes_out);
+/* *route = the name sp_last_route() would report after sp_conv2d_igemm(p), without launching anything (same argument checks, same
+ * errors; host-only: callable without a GPU).  It looks at p->workspace / workspace_bytes / split_sync but never dereferences a pointer. */
+int sp_conv2d_route(const sp_conv_params* p, const char** route);
 
 /* Weight gradient of the same convolution (autograd of nn.Conv2d at model_wrapper.py:160,188):
  *   dw[co][tap][ci] (+)= sum_{n,h,w} dy[n,h,w,co] * x[n,h+dr,w+ds,ci]      fp32, layout [cout][taps][cin_p]

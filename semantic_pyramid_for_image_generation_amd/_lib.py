@@ -137,6 +137,13 @@ def lib():
     return _lib
 
 
+def conv_route(p: SpConvParams) -> str:
+    """The kernel sp_conv2d_igemm would launch for `p` (include/sempyr.h: sp_conv2d_route; host-only, works without a GPU)."""
+    out = ctypes.c_char_p()
+    call("sp_conv2d_route", ctypes.byref(p), ctypes.byref(out))
+    return out.value.decode()
+
+
 def call(name: str, *args) -> None:
     """Calls an int-returning entry point and raises SempyrError (with the library's message) on failure."""
     rc = getattr(lib(), name)(*args)

@@ -33,6 +33,17 @@ int main(void) {
                                 EXPECT(sp_conv2d_wgrad_workspace(batches[b], maps[m], maps[m], cin_p, chans[o], k, dt, &floats) == SP_OK && floats >= 0, "wgrad workspace");
                                 queries += 2;
                             }
+                            // the route query on the same shape, with and without the scratch the query above sized (pointers are never read)
+                            sp_conv_params q;
+                            memset(&q, 0, sizeof q);
+                            q.x = q.w = q.y = &queries;
+                            q.n = batches[b]; q.h = q.w_ = maps[m]; q.cin_p = cin_p; q.cout = q.ldy = chans[o]; q.ksize = k; q.dtype = dt;
+                            for (int lend = 0; lend < 2; ++lend) {
+                                const char* route = NULL;
+                                q.workspace = lend ? &queries : NULL; q.workspace_bytes = lend ? bytes : 0; q.split_sync = lend ? (int32_t*)&queries : NULL;
+                                EXPECT(sp_conv2d_route(&q, &route) == SP_OK && route != NULL && strlen(route) > 0, "conv route");
+                                ++queries;
+                            }
                             sp_set_tuning(SP_TUNE_DETERMINISTIC, -1);
                         }
     // argument-check failure paths of the launching entry points (they return before touching the device)
@@ -50,6 +61,10 @@ int main(void) {
     p.dtype = SP_BF16; p.pool2 = 3; EXPECT(sp_conv2d_igemm(&p, NULL) == SP_ERR_INVALID, "pool2 range");
     p.pool2 = 1; p.cout = 24; p.ldy = 24; EXPECT(sp_conv2d_igemm(&p, NULL) == SP_ERR_INVALID, "pool2 shape");
     p.pool2 = 0; p.in_up2 = 1; p.ksize = 1; EXPECT(sp_conv2d_igemm(&p, NULL) == SP_ERR_INVALID, "in_up2 shape");
+    const char* route = NULL;
+    p.in_up2 = 0; p.ksize = 3; p.cout = 64; p.ldy = 64; p.tail_w = p.tail_y = &dummy; p.tail_cout = 3; p.tail_ld = 3;
+    EXPECT(sp_conv2d_route(&p, &route) == SP_ERR_UNSUPPORTED, "route: tail on 8 rows");
+    EXPECT(sp_conv2d_route(NULL, &route) == SP_ERR_INVALID && sp_conv2d_route(&p, NULL) == SP_ERR_INVALID, "route null");
     int64_t out;
     EXPECT(sp_conv2d_workspace(0, 8, 8, 8, 8, 3, SP_BF16, &out) == SP_ERR_INVALID, "workspace bad dims");
     EXPECT(sp_conv2d_wgrad_workspace(1, 8, 8, 8, 8, 2, SP_BF16, &out) == SP_ERR_INVALID, "wgrad workspace bad ksize");

@@ -185,10 +185,12 @@ extern int* const sp_g_tune;
 static inline int sp_tune(int key, int dflt) { return sp_g_tune[key] >= 0 ? sp_g_tune[key] : dflt; }
 // fixed-order reductions (no fp32 atomics): always in the fp32 parity mode, on request in the bf16 throughput mode
 static inline bool sp_deterministic(int dtype) { return sp_g_tune[SP_TUNE_DETERMINISTIC] >= 0 ? sp_g_tune[SP_TUNE_DETERMINISTIC] != 0 : dtype == SP_F32; }
-// conv_pp.hip: SP_OK after launching, 1 if the shape is not covered (bf16 3x3, Cout > 64, th x 32 patches with th = 8 / 16)
-int sp_conv_pp_launch(const sp_conv_params& p, int th, hipStream_t s);
-int sp_conv_ppw_launch(const sp_conv_params& p, hipStream_t s);      // conv_ppw.hip: 128 co x 16 x 32 px, 64 co x 4 rows per wave
-int sp_conv_ppw_covers(const sp_conv_params& p);                    // ... whether it takes the launch at all (shape, epilogue)
+// conv_pp.hip, kernel = CK_PP_8ROW / CK_PP_16ROW / CK_PP_W16 (conv_common.h): the instantiation that takes the launch as CV_* bits, -1 if
+// none does (pure: shape, epilogue, tuning table); the launcher is for what the predicate admits
+int sp_conv_pp_form(const sp_conv_params& p, int kernel);
+int sp_conv_pp_launch(const sp_conv_params& p, int kernel, hipStream_t s);
+int sp_conv_ppw_form(const sp_conv_params& p);                       // conv_ppw.hip (128 co x 16 x 32 px, 64 co x 4 rows per wave): the same pair
+int sp_conv_ppw_launch(const sp_conv_params& p, hipStream_t s);
 // reduce_queue.hip (compiled once, shared by both flavours): true = the slab reduction was queued for sp_wgrad_reduce_flush
 bool spq_push_reduce(const float* slabs, int nsplit, long n_dw, float* dw, const float* bias_slabs, int bias_ld, int cout, float* dbias);
 // conv_wgrad_rows.hip: SP_OK after launching, 1 if the shape is not covered

@@ -243,8 +243,42 @@ inline bool conv_operands_below_1g(const sp_conv_params& p, long esz) {
     return (long)p.n * p.h * p.w_ * p.cin_p * esz < (1L << 30) && (long)p.cout * p.ksize * p.ksize * p.cin_p * esz < (1L << 30);
 }
 
+// ---- The forward route: the kernel sp_conv2d_igemm launches for a parameter block.  conv_igemm.hip's conv_plan() decides it without
+// touching the device, dispatch() launches it, sp_conv2d_route() reports it.
+constexpr int NUM_CU = 256;                   // MI355X: the persistent kernels run one block per CU, and time goes by rounds of them
+enum ConvKernel { CK_UNSUPPORTED, CK_THINCO, CK_CIN8, CK_1X1_SPLITK, CK_1X1_DIRECT, CK_HALO_64, CK_HALO_128, CK_TALL_1_16, CK_TALL_2_16, CK_TALL_2_8,
+                  CK_PP_8ROW, CK_PP_16ROW, CK_PP_W16, CK_PPW, CK_IGEMM_DMA, CK_IGEMM };
+// the instantiation within the family, as bits (0: the general one).  FAST / TIMING / IDX / TAIL / F8: conv_pp.hip's template flags
+// (IDX also the halo and tall kernels'); POOL / TIMING / LA: conv_ppw.hip's; SPLITK: the LDS-DMA igemm with its finalize pass
+enum { CV_FAST = 1, CV_TIMING = 2, CV_IDX = 4, CV_TAIL = 8, CV_F8 = 16, CV_POOL = 32, CV_LA = 64, CV_SPLITK = 128 };
+struct ConvRoute {
+    int kernel, form;               // ConvKernel, CV_* bits
+    int co_t, px_t, ksplit;         // the igemm kernels' output tile, the LDS-DMA one's K splits
+    const char* error;              // CK_UNSUPPORTED: the message
+};
+// sp_last_route() / sp_conv2d_route(): the one place the names live - bench.py's route tables and the tests match on them
+inline const char* conv_route_name(int kernel, int form, bool f32) {
+    switch (kernel) {
+        case CK_THINCO: return "conv3x3_thinco";
+        case CK_CIN8: return "conv3x3_cin8";
+        case CK_1X1_SPLITK: return "conv1x1_splitk";
+        case CK_1X1_DIRECT: return "conv1x1_direct";
+        case CK_HALO_64: case CK_HALO_128: return f32 ? "conv3x3_halo<f32>" : "conv3x3_halo<16bit>";
+        case CK_TALL_1_16: return f32 ? "conv3x3_tall<f32,1,16>" : "conv3x3_tall<16bit,1,16>";
+        case CK_TALL_2_16: return f32 ? "conv3x3_tall<f32,2,16>" : "conv3x3_tall<16bit,2,16>";
+        case CK_TALL_2_8: return f32 ? "conv3x3_tall<f32,2,8>" : "conv3x3_tall<16bit,2,8>";
+        case CK_PP_8ROW: return (form & CV_F8) ? "conv3x3_pp<f8,2>" : (form & CV_FAST) ? "conv3x3_pp<16bit,2,FAST>" : "conv3x3_pp<16bit,2>";
+        case CK_PP_16ROW: return (form & CV_FAST) ? "conv3x3_pp<16bit,1,FAST>" : "conv3x3_pp<16bit,1>";
+        case CK_PP_W16: return "conv3x3_pp<16bit,2,FAST,w16>";
+        case CK_PPW: return "conv3x3_ppw<16bit> (64 co x 4 rows per wave)";
+        case CK_IGEMM_DMA: return (form & CV_SPLITK) ? "conv_igemm_dma+finalize (split-K)" : "conv_igemm_dma";
+        case CK_IGEMM: return "conv_igemm (register-staged)";
+    }
+    return "";
+}
+
 // Work items of the ping-pong forms on these dims, 0 where the form does not take them: the admission of its launcher on the dims
-// (sp_conv_pp_launch / sp_conv_ppw_covers add the epilogue's), shared with sp_conv2d_workspace().
+// (sp_conv_pp_form / sp_conv_ppw_form add the epilogue's), shared with sp_conv2d_workspace().
 inline long pp_items_8row(int n, int h, int w, int cout) {            // conv_pp.hip: 128 co x 8 x 32 px
     return h % 8 != 0 || w % 32 != 0 || cout <= 64 ? 0 : (long)n * (h / 8) * (w / 32) * ((cout + 127) / 128);
 }
@@ -258,10 +292,12 @@ inline long pp_items_w16(int n, int h, int w, int cout) {             // conv_pp
 inline long ppw_items(int n, int h, int w, int cout) {                // conv_ppw.hip: 128 co x 16 x 32 px
     return h % 16 != 0 || w % 32 != 0 || cout <= 64 ? 0 : (long)n * (h / 16) * (w / 32) * ((cout + 127) / 128);
 }
+inline long pp_items(int kernel, int n, int h, int w, int cout) {     // ... by form (CK_PP_8ROW / CK_PP_16ROW / CK_PP_W16)
+    return kernel == CK_PP_W16 ? pp_items_w16(n, h, w, cout) : kernel == CK_PP_16ROW ? pp_items_16row(n, h, w, cout) : pp_items_8row(n, h, w, cout);
+}
 
 // ---- K-split of the LAST, partial round of a ping-pong launch ("tail split"; the scheme and its hand-over: the top of conv_pp.hip).
 // The plan serves the launchers and sp_conv2d_workspace(), the piece decoding below the kernels.
-constexpr int SK_NUM_CU = 256;                // MI355X: the persistent ping-pong kernels run one block per CU
 constexpr int SK_MAX_PARTS = 4;
 // The last round takes `chunk` per 32-channel chunk of its longest piece plus, per piece handed over, `near` (two full rounds or more
 // in front of the owner's piece hide more of it) or `far`; a piece is `slab_floats` fp32 values (8 waves x 64 lanes x accumulators).
@@ -278,26 +314,26 @@ struct TailSplit { int parts, tail_items, grid; };
 // round: e.g. 80 items of 128 co x 16 x 16 px for 512 -> 512 on 16 x 16 maps at batch 20): every item is a tail item and the grid is
 // tail_items * parts blocks of one piece each (SP_TUNE_CONV_PP_SPLIT = 2 keeps the split to launches of at least one full round).
 inline TailSplit tail_split_plan(int total, int kchunks, const TailSplitModel& m, long workspace_bytes) {
-    TailSplit r{0, 0, total < SK_NUM_CU ? total : SK_NUM_CU};
+    TailSplit r{0, 0, total < NUM_CU ? total : NUM_CU};
     // (less than one round: one block per item - rounded down to a multiple of 8 for the XCD remap, 100 items became 96 blocks of
     // which four took two items, i.e. two rounds; the kernels skip the remap when the grid is not a multiple of 8)
     const int mode = sp_tune(SP_TUNE_CONV_PP_SPLIT, 1);
-    if (!mode || total <= 0 || (total < SK_NUM_CU && mode == 2)) return r;
-    const int R = total % SK_NUM_CU;
+    if (!mode || total <= 0 || (total < NUM_CU && mode == 2)) return r;
+    const int R = total % NUM_CU;
     if (R == 0) return r;
-    int pmax = SK_NUM_CU / R;
+    int pmax = NUM_CU / R;
     if (pmax > SK_MAX_PARTS) pmax = SK_MAX_PARTS;
     // a piece has at least two chunks, and the split must save at least a twentieth of the round
     int P = 1;
     long best = m.chunk * kchunks;
-    const long handover = total >= 2 * SK_NUM_CU ? m.near : m.far;
+    const long handover = total >= 2 * NUM_CU ? m.near : m.far;
     for (int q = 2; q <= pmax && kchunks / q >= 2; ++q) {
         const long c = m.chunk * ((kchunks + q - 1) / q) + handover * (q - 1);
         if (c < best && 20 * c < 19 * m.chunk * kchunks) { best = c; P = q; }
     }
     if (P < 2 || (long)R * P * m.slab_floats * 4 > workspace_bytes) return r;
     r.parts = P; r.tail_items = R;
-    r.grid = total < SK_NUM_CU ? R * P : SK_NUM_CU;
+    r.grid = total < NUM_CU ? R * P : NUM_CU;
     return r;
 }
 // sp_conv2d_workspace(): bytes of fp32 scratch with which a launch of `items` items splits its last round (0: it would not)
@@ -319,9 +355,9 @@ inline long pp_rounds100(long total, int cin_p, long workspace_bytes) {
     const int kchunks = (cin_p + 31) / 32;
     if (total < (1L << 30)) {
         const TailSplit sk = tail_split_plan((int)total, kchunks, SK_PP, workspace_bytes);
-        if (sk.parts > 1 && total >= SK_NUM_CU) return 100 * (total / SK_NUM_CU) + 100 / sk.parts + 162 * (sk.parts - 1) / kchunks + 1;
+        if (sk.parts > 1 && total >= NUM_CU) return 100 * (total / NUM_CU) + 100 / sk.parts + 162 * (sk.parts - 1) / kchunks + 1;
     }
-    return 100 * ((total + SK_NUM_CU - 1) / SK_NUM_CU);
+    return 100 * ((total + NUM_CU - 1) / NUM_CU);
 }
 
 // The piece decoding in the kernels: sk_arg first thing, then (assign) the block's share - the first full_total items go round robin as

@@ -445,7 +445,7 @@ int launch_halo(const sp_conv_params& p, hipStream_t s) {
     constexpr auto kern = conv3x3_halo_kernel<T, CO_T, TPS, IDX>;
     if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     dim3 grid((unsigned)(p.n * (p.h / HALO_TH) * (p.w_ / HALO_TW) * ((p.cout + CO_T - 1) / CO_T)));
-    sp_note_route(sizeof(T) == 4 ? "conv3x3_halo<f32>" : "conv3x3_halo<16bit>");
+    sp_note_route(conv_route_name(CK_HALO_64, 0, sizeof(T) == 4));
     hipLaunchKernelGGL(kern, grid, dim3(CO_T * 4), LDS, s, p);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -691,7 +691,6 @@ __global__ void conv_finalize_kernel(sp_conv_params p, int ksplit) {
 // side: lane (row, ps) fetches logical slot ps ^ key.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int TL_TH = 16, TL_TW = 32, TL_HR = TL_TH + 2;
-constexpr int g_num_cu = 256;                          // MI355X
 
 
 // WCO = 2: 128 co per block, a wave = 64 co x (4 rows x 32 cols);  WCO = 1: 64 co per block, a wave = 64 co x (2 rows x 32).
@@ -1033,11 +1032,10 @@ int launch_tall(const sp_conv_params& p, hipStream_t s) {
     if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const int cotiles = (p.cout + 64 * WCO - 1) / (64 * WCO);
     const int total = p.n * (p.h / TH) * (p.w_ / TL_TW) * cotiles;
-    int grid = total < g_num_cu ? total : g_num_cu;        // persistent: one block per CU
+    int grid = total < NUM_CU ? total : NUM_CU;            // persistent: one block per CU
     if (grid >= 8) grid -= grid % 8;
     // measured (scratch/ab_conv.py, profiles/README.md): staggering helps the 16-row 128-co tile (+3-5 %) and costs the 8-row one 4 %
-    sp_note_route(sizeof(T) == 4 ? (WCO == 1 ? "conv3x3_tall<f32,1,16>" : TH == 16 ? "conv3x3_tall<f32,2,16>" : "conv3x3_tall<f32,2,8>")
-                                 : (WCO == 1 ? "conv3x3_tall<16bit,1,16>" : TH == 16 ? "conv3x3_tall<16bit,2,16>" : "conv3x3_tall<16bit,2,8>"));
+    sp_note_route(conv_route_name(WCO == 1 ? CK_TALL_1_16 : TH == 16 ? CK_TALL_2_16 : CK_TALL_2_8, 0, sizeof(T) == 4));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, s, p, cotiles, total, sp_tune(SP_TUNE_CONV_STAGGER, (WCO == 2 && TH == 16) ? 1 : 0));
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1048,13 +1046,28 @@ int launch_tall(const sp_conv_params& p, hipStream_t s) {
 // launches are latency-bound, larger tiles do not pay by themselves) - except where its tile count lands between one and two rounds
 // of the 256 CUs and K is long: 512 -> 512 on 8 x 8 maps at batch 40 has 320 tiles of 72 K-steps each (no split: 1.25 rounds, 36.5
 // us); 160 tiles of 128 co x 64 px split K three ways (480 blocks of 24 steps: 28.3 us).
+inline int igemm_nk(int cin_p, int ksize, int dtype) {                // K-steps of 128 bytes per tap
+    const int e = dtype == SP_F32 ? 4 : 8;
+    return ksize * ksize * ((cin_p + 8 * e - 1) / (8 * e));
+}
 inline int igemm_small_tile(long M, int cout, int cin_p, int ksize, int dtype) {
     const int forced = sp_tune(SP_TUNE_IGEMM_TILE, -1);
     if (forced >= 0) return forced;
     const long tiles64 = ((M + 63) / 64) * ((cout + 63) / 64);
-    const int e = dtype == SP_F32 ? 4 : 8;
-    const int nk = ksize * ksize * ((cin_p + 8 * e - 1) / (8 * e));
-    return (tiles64 > 256 && tiles64 <= 512 && nk >= 48 && cout % 128 == 0) ? 2 : 0;
+    return (tiles64 > 256 && tiles64 <= 512 && igemm_nk(cin_p, ksize, dtype) >= 48 && cout % 128 == 0) ? 2 : 0;
+}
+// The igemm kernels' output tile {co, px}, of the LDS-DMA kernel (`dma`) or the register-staged one; tile_key: the launchers' switch
+struct IgemmTile { int co_t, px_t; };
+constexpr int tile_key(int co_t, int px_t) { return co_t * 1024 + px_t; }
+inline IgemmTile igemm_tile(bool dma, long M, int cout, int cin_p, int ksize, int dtype) {
+    if (cout <= 64) return {cout <= 16 ? 16 : cout <= 32 ? 32 : 64, 256};     // (16 co: register-staged only, the LDS-DMA kernel takes cout > 16)
+    if (M > 8192) return {128, 128};
+    switch (dma ? igemm_small_tile(M, cout, cin_p, ksize, dtype) : 0) {
+        case 1: return {128, 128};
+        case 2: return {128, 64};
+        case 3: return {64, 128};
+        default: return {64, 64};                                             // (tiny spatial: more blocks)
+    }
 }
 
 // number of K splits for `tiles` output tiles and nk K-steps: aim at ~1.5 blocks per CU, at least 6 K-steps per split
@@ -1068,29 +1081,33 @@ inline int split_k_plan(int tiles, int nk) {
     if (ksplit > 16) ksplit = 16;
     return ksplit < 1 ? 1 : ksplit;
 }
+// ... of the LDS-DMA igemm on tile `t`: what sp_conv2d_workspace() sizes the scratch for
+inline int igemm_ksplit_wanted(IgemmTile t, long M, int cout, int cin_p, int ksize, int dtype) {
+    return split_k_plan((int)((M + t.px_t - 1) / t.px_t) * ((cout + t.co_t - 1) / t.co_t), igemm_nk(cin_p, ksize, dtype));
+}
+// ... and what a launch does: split-K where the output tiles cannot fill the chip and the caller lent an fp32 workspace of ksplit
+// slabs [M][cout]: every split stores its partial tile with plain stores, conv_finalize_kernel sums the slabs (no fill, no atomics -
+// the first version met in one slab through fp32 atomics and spent most of its time there: 4x4 layers 41 -> 15 us)
+inline int igemm_ksplit(const sp_conv_params& p, IgemmTile t) {
+    const long M = (long)p.n * p.h * p.w_;
+    int ksplit = p.workspace == nullptr ? 1 : igemm_ksplit_wanted(t, M, p.cout, p.cin_p, p.ksize, p.dtype);
+    while (ksplit > 1 && p.workspace_bytes < (int64_t)ksplit * M * p.cout * 4) --ksplit;
+    if (ksplit > 1) {
+        const int nk = igemm_nk(p.cin_p, p.ksize, p.dtype), per = (nk + ksplit - 1) / ksplit;
+        ksplit = (nk + per - 1) / per;                 // every split owns at least one K-step, so every slab is fully written
+    }
+    return ksplit;
+}
 
 template <typename T, int WCO, int WPX, int FCO, int FPX>
-int launch_dma(const sp_conv_params& p, hipStream_t s) {
+int launch_dma(const sp_conv_params& p, int ksplit, hipStream_t s) {
     constexpr int CO_T = WCO * FCO * 16, PX_T = WPX * FPX * 16;
     constexpr int LDS = 3 * (CO_T + PX_T) * 128;
     constexpr auto kern = conv_igemm_dma_kernel<T, WCO, WPX, FCO, FPX>;
     if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const long M = (long)p.n * p.h * p.w_;
-    const int tiles = (int)((M + PX_T - 1) / PX_T) * ((p.cout + CO_T - 1) / CO_T);
-    const int e = p.dtype == SP_F32 ? 4 : 8;
-    const int nk = p.ksize * p.ksize * ((p.cin_p + 8 * e - 1) / (8 * e));
-    // split-K where the output tiles cannot fill the chip and the caller lent an fp32 workspace of ksplit slabs [M][cout]:
-    // every split stores its partial tile with plain stores, conv_finalize_kernel sums the slabs (no fill, no atomics -
-    // the first version met in one slab through fp32 atomics and spent most of its time there: 4x4 layers 41 -> 15 us)
-    int ksplit = split_k_plan(tiles, nk);
-    if (p.workspace == nullptr) ksplit = 1;
-    while (ksplit > 1 && p.workspace_bytes < (int64_t)ksplit * M * p.cout * 4) --ksplit;
-    if (ksplit > 1) {
-        const int per = (nk + ksplit - 1) / ksplit;
-        ksplit = (nk + per - 1) / per;                 // every split owns at least one K-step, so every slab is fully written
-    }
     dim3 grid((unsigned)((M + PX_T - 1) / PX_T), (unsigned)((p.cout + CO_T - 1) / CO_T), (unsigned)ksplit);
-    sp_note_route(ksplit > 1 ? "conv_igemm_dma+finalize (split-K)" : "conv_igemm_dma");
+    sp_note_route(conv_route_name(CK_IGEMM_DMA, ksplit > 1 ? CV_SPLITK : 0, false));
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, p, ksplit);
     SP_LAUNCH_CHECK();
     if (ksplit > 1) {
@@ -1110,7 +1127,7 @@ int launch_cfg(const sp_conv_params& p, hipStream_t s) {
     if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const long M = (long)p.n * p.h * p.w_;
     dim3 grid((unsigned)((M + PX_T - 1) / PX_T), (unsigned)((p.cout + CO_T - 1) / CO_T));
-    sp_note_route("conv_igemm (register-staged)");
+    sp_note_route(conv_route_name(CK_IGEMM, 0, false));
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, p);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1208,7 +1225,7 @@ int launch_1x1_direct(const sp_conv_params& p, hipStream_t s) {
     long gx = (M + 127) / 128;                                           // one 32-pixel group per wave and pass at most
     const long cap = 1024 / cotiles > 0 ? 1024 / cotiles : 1;
     if (gx > cap) gx = cap;
-    sp_note_route("conv1x1_direct");
+    sp_note_route(conv_route_name(CK_1X1_DIRECT, 0, false));
     hipLaunchKernelGGL(conv1x1_direct_kernel, dim3((unsigned)gx, (unsigned)cotiles), dim3(256), lds, s, p, row_bytes);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1306,7 +1323,7 @@ int launch_1x1_splitk(const sp_conv_params& p, hipStream_t s) {
     const int ksteps = (p.cin_p + 31) / 32;
     const long M = (long)p.n * p.h * p.w_;
     dim3 grid((unsigned)((M + 31) / 32), (unsigned)((p.cout + 63) / 64));
-    sp_note_route("conv1x1_splitk");
+    sp_note_route(conv_route_name(CK_1X1_SPLITK, 0, false));
     if (ksteps <= 8) hipLaunchKernelGGL(conv1x1_splitk_kernel<2>, grid, dim3(256), 0, s, p);
     else if (ksteps <= 16) hipLaunchKernelGGL(conv1x1_splitk_kernel<4>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(conv1x1_splitk_kernel<6>, grid, dim3(256), 0, s, p);
@@ -1413,7 +1430,7 @@ __global__ __launch_bounds__(256) void conv3x3_cin8_kernel(sp_conv_params p) {
 
 int launch_cin8(const sp_conv_params& p, hipStream_t s) {
     const long blocks = (long)p.n * (p.h / C8_TH) * (p.w_ / C8_TW);
-    sp_note_route("conv3x3_cin8");
+    sp_note_route(conv_route_name(CK_CIN8, 0, false));
     hipLaunchKernelGGL(conv3x3_cin8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1504,76 +1521,101 @@ int launch_thinco(const sp_conv_params& p, hipStream_t s) {
     constexpr int LDS = TN_HH * TN_HW * (KC * 64 + 16);
     if (const int rc = sp_lds_limit<conv3x3_thinco_kernel<KC>>(LDS)) return rc;
     const long blocks = (long)p.n * (p.h / TN_TH) * (p.w_ / TN_TW);
-    sp_note_route("conv3x3_thinco");
+    sp_note_route(conv_route_name(CK_THINCO, 0, false));
     hipLaunchKernelGGL(conv3x3_thinco_kernel<KC>, dim3((unsigned)blocks), dim3(256), LDS, s, p);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
 
-template <typename T>
-int dispatch(const sp_conv_params& p, hipStream_t s) {
+// 3x3 layers on whole (8 x 32)-pixel patches with enough output channels for the halo-reuse kernels (halo, tall, ping-pong)
+inline bool conv_halo_path(long M, int h, int w, int cin_p, int cout, int ksize) {
+    // cout <= 16 on a big feature map (the generator's RGB head, 64 -> 3 @256^2): memory-bound; the halo-reuse kernels read
+    // the input once instead of once per tap, which outweighs the idle MFMA rows (158 -> ~85 us)
+    const bool thin_big = cout <= 16 && cin_p >= 32 && M >= (1L << 18);
+    return ksize == 3 && (cout > 32 || thin_big) && h % HALO_TH == 0 && w % HALO_TW == 0;
+}
+// 16-wide maps, Cout > 64, 16-bit: the ping-pong kernel on 16 x 16-pixel tiles (conv_pp.hip; SP_TUNE_CONV_PP = 0 or 2 keeps the
+// LDS-DMA igemm)
+inline bool conv_w16_path(int w, int cout, int ksize, bool h16) {
+    const int ppm = sp_tune(SP_TUNE_CONV_PP, 1);
+    return h16 && ksize == 3 && w == 16 && cout > 64 && (ppm == 1 || ppm == 3);
+}
+// LDS-DMA kernel: measured faster for the small-spatial 3x3 layers (latency-bound), slower for 1x1 (profiles/README.md);
+// SP_IGEMM_DMA=2 forces it everywhere, 0 disables it
+inline bool conv_dma_path(long M, int cout, int ksize) {
+    const int dma_mode = sp_tune(SP_TUNE_IGEMM_DMA, 1);
+    return cout > 16 && (dma_mode == 2 || (dma_mode == 1 && ksize == 3 && M <= 8192));
+}
+
+// The route of a checked parameter block (conv_check_args): pure - the parameters and the tuning table, no HIP call.
+ConvRoute conv_plan(const sp_conv_params& p) {
+    const auto route = [](int kernel, int form = 0) { return ConvRoute{kernel, form, 0, 0, 1, nullptr}; };
+    const auto unsupported = [](const char* msg) { return ConvRoute{CK_UNSUPPORTED, 0, 0, 0, 1, msg}; };
+    int form;
+    if (p.dtype == SP_F8) {
+        // BASELINE.json config 5: e4m3 operands on the fp8 MFMA, the ping-pong 3x3 kernel only (conv_pp.hip)
+        if ((form = sp_conv_pp_form(p, CK_PP_8ROW)) >= 0) return route(CK_PP_8ROW, form);
+        return unsupported("sp_conv2d_igemm: SP_F8 covers 3x3 layers with cout > 64, h %% 8 == 0, w %% 32 == 0 only");
+    }
+    const bool h16 = p.dtype != SP_F32;
+    const int esz = h16 ? 2 : 4, idx = p.pool_idx != nullptr ? CV_IDX : 0;
+    const int pp_mode = h16 ? sp_tune(SP_TUNE_CONV_PP, 1) : 0, tall_mode = sp_tune(SP_TUNE_CONV_TALL, 1);
+    if (p.tail_w != nullptr) {
+        // fused 1x1 tail: the 64-channel FAST form of the ping-pong kernel only - no silent fall-back to a kernel that would ignore it
+        if (!p.in_up2 && p.img_scale == nullptr && pp_mode && tall_mode == 1 && (form = sp_conv_pp_form(p, CK_PP_16ROW)) >= 0) return route(CK_PP_16ROW, form);
+        return unsupported("sp_conv2d_igemm: the fused 1x1 tail needs 16-bit storage, a 3x3 layer with cout == 64, h %% 16 == 0, w %% 32 == 0, ldy %% 8 == 0, no pooling");
+    }
     const long M = (long)p.n * p.h * p.w_;
-    if (sizeof(T) == 2 && p.ksize == 3 && p.cout <= 4 && (p.cin_p == 32 || p.cin_p == 64) && !p.pool2 && !p.in_up2 && p.h % TN_TH == 0 &&
-        p.w_ % TN_TW == 0 && sp_tune(SP_TUNE_CONV_THINCO, 1) && sp_tune(SP_TUNE_CONV_TALL, 1) <= 1)
-        return p.cin_p == 64 ? launch_thinco<2>(p, s) : launch_thinco<1>(p, s);
-    if (sizeof(T) == 2 && p.ksize == 3 && p.cin_p == 8 && p.cout % 16 == 0 && p.cout <= 64 && (p.ldy & 7) == 0 && !p.pool2 && !p.in_up2 &&
-        p.h % C8_TH == 0 && p.w_ % C8_TW == 0 && sp_tune(SP_TUNE_CONV_CIN8, 1) && sp_tune(SP_TUNE_CONV_TALL, 1) <= 1)   // (forced tall modes: tests)
-        return launch_cin8(p, s);
-    if (sizeof(T) == 2 && p.ksize == 1 && p.cin_p > 1024 && ((M + 31) / 32) * ((p.cout + 63) / 64) <= sp_tune(SP_TUNE_CONV1X1_SPLITK, 320))
-        return launch_1x1_splitk(p, s);                 // (small maps only: the wide networks' deepest 1x1 input gradients; larger maps fall through)
-    if (sizeof(T) == 2 && p.ksize == 1 && p.cin_p <= 1024) {
+    if (h16 && p.ksize == 3 && p.cout <= 4 && (p.cin_p == 32 || p.cin_p == 64) && !p.pool2 && !p.in_up2 && p.h % TN_TH == 0 &&
+        p.w_ % TN_TW == 0 && sp_tune(SP_TUNE_CONV_THINCO, 1) && tall_mode <= 1)
+        return route(CK_THINCO);
+    if (h16 && p.ksize == 3 && p.cin_p == 8 && p.cout % 16 == 0 && p.cout <= 64 && (p.ldy & 7) == 0 && !p.pool2 && !p.in_up2 &&
+        p.h % C8_TH == 0 && p.w_ % C8_TW == 0 && sp_tune(SP_TUNE_CONV_CIN8, 1) && tall_mode <= 1)   // (forced tall modes: tests)
+        return route(CK_CIN8);
+    if (h16 && p.ksize == 1) {
         // small maps: K split over the waves of a block, as long as the blocks (32 pixels x 64 channels each, every one
         // streaming its whole 64 x Cin weight tile from L2) stay few: beyond ~320 the LDS-staged tile of the direct kernel wins
         const int ks = (p.cin_p + 31) / 32;
-        const long blocks = ((M + 31) / 32) * ((p.cout + 63) / 64);
-        if (ks >= 4 && ks <= 24 && blocks <= sp_tune(SP_TUNE_CONV1X1_SPLITK, 320)) return launch_1x1_splitk(p, s);
-        if (sp_tune(SP_TUNE_CONV1X1_DIRECT, 1)) return launch_1x1_direct(p, s);
+        const bool few_blocks = ((M + 31) / 32) * ((p.cout + 63) / 64) <= sp_tune(SP_TUNE_CONV1X1_SPLITK, 320);
+        // (cin_p > 1024, small maps only: the wide networks' deepest 1x1 input gradients; larger maps fall through)
+        if (few_blocks && (p.cin_p > 1024 || (ks >= 4 && ks <= 24))) return route(CK_1X1_SPLITK);
+        if (p.cin_p <= 1024 && sp_tune(SP_TUNE_CONV1X1_DIRECT, 1)) return route(CK_1X1_DIRECT);
     }
-    // cout <= 16 on a big feature map (the generator's RGB head, 64 -> 3 @256^2): memory-bound; the halo-reuse kernels read
-    // the input once instead of once per tap, which outweighs the idle MFMA rows (158 -> ~85 us)
-    if (p.pool_idx != nullptr) {
+    const bool fits30 = conv_operands_below_1g(p, esz);
+    if (idx) {
         // ReLU + MaxPool with recorded window positions (pool2 == 2, the API checked h % 8 == 0, w % 32 == 0, cout > 32, cout % 16 == 0):
         // its own instantiations of a fixed set of kernels, so that the hot ones keep their register allocation - 16-bit: the
-        // ping-pong kernel's general epilogue (64 co x 16x32 / 128 co x 8x32 tiles); fp32, and what the ping-pong launcher declines:
+        // ping-pong kernel's general epilogue (64 co x 16x32 / 128 co x 8x32 tiles); fp32, and what the ping-pong form declines:
         // the LDS-DMA tall kernel on the same tiles; Cout <= 64 with h % 16 != 0: the register-staged halo kernel
-        if (p.cout <= 64 && p.h % TL_TH != 0) return launch_halo<T, 64, 1, true>(p, s);
-        if (!conv_operands_below_1g(p, sizeof(T))) { sp_set_error("sp_conv2d_igemm: pool_idx needs operands below 1 GiB (n*h*w*cin_p, cout*9*cin_p)"); return SP_ERR_UNSUPPORTED; }
-        if (sizeof(T) == 2 && sp_tune(SP_TUNE_CONV_PP, 1)) {
-            const int rc = sp_conv_pp_launch(p, p.cout <= 64 ? 16 : 8, s);
-            if (rc != 1) return rc;
-        }
-        return p.cout <= 64 ? launch_tall<T, 1, 16, true>(p, s) : launch_tall<T, 2, 8, true>(p, s);
+        if (p.cout <= 64 && p.h % TL_TH != 0) return route(CK_HALO_64, idx);
+        if (!fits30) return unsupported("sp_conv2d_igemm: pool_idx needs operands below 1 GiB (n*h*w*cin_p, cout*9*cin_p)");
+        const int pp = p.cout <= 64 ? CK_PP_16ROW : CK_PP_8ROW;
+        if (pp_mode && (form = sp_conv_pp_form(p, pp)) >= 0) return route(pp, form);
+        return route(p.cout <= 64 ? CK_TALL_1_16 : CK_TALL_2_8, idx);
     }
-    const bool thin_big = p.cout <= 16 && p.cin_p >= 32 && M >= (1L << 18);
-    if (p.ksize == 3 && (p.cout > 32 || thin_big) && p.h % HALO_TH == 0 && p.w_ % HALO_TW == 0) {
+    if (conv_halo_path(M, p.h, p.w_, p.cin_p, p.cout, p.ksize)) {
         // persistent tall kernel (half the LDS reads per MFMA, LDS-DMA pipeline across tiles); SP_CONV_TALL=0 disables, 2 forces
-        const int tall_mode = sp_tune(SP_TUNE_CONV_TALL, 1);
-        const bool fits30 = conv_operands_below_1g(p, sizeof(T));
         const bool tall_ok = tall_mode && fits30 && p.h % TL_TH == 0 && p.w_ % TL_TW == 0;
         if (p.cout <= 64) {
             // bf16, 16 < Cout <= 64 on 16-row patches: the ping-pong schedule with 8 row-pair waves (conv_pp.hip, WCO = 1)
-            if (tall_ok && sizeof(T) == 2 && p.cout > 16 && tall_mode <= 1 && sp_tune(SP_TUNE_CONV_PP, 1) && !(sp_tune(SP_TUNE_CONV_PP, 1) & 32)) {
-                const int rc = sp_conv_pp_launch(p, 16, s);
-                if (rc != 1) return rc;
-            }
-            if (tall_ok) return launch_tall<T, 1>(p, s);
-            return launch_halo<T, 64, 1>(p, s);
+            if (tall_ok && p.cout > 16 && tall_mode <= 1 && pp_mode && !(pp_mode & 32) && (form = sp_conv_pp_form(p, CK_PP_16ROW)) >= 0)
+                return route(CK_PP_16ROW, form);
+            return route(tall_ok ? CK_TALL_1_16 : CK_HALO_64);
         }
         // one block per CU for the tall and the ping-pong kernels, so time ~ rounds over the 256 CUs x time per block: bt 16-row
         // items (rt rounds) or 2 bt 8-row items (rh)
         const long bt = (long)p.n * (p.h / TL_TH) * (p.w_ / TL_TW) * ((p.cout + 127) / 128);
-        const long rt = (bt + 255) / 256, rh = (2 * bt + 255) / 256;
+        const long rt = (bt + NUM_CU - 1) / NUM_CU, rh = (2 * bt + NUM_CU - 1) / NUM_CU;
         // bf16: the ping-pong schedule (conv_pp.hip) on the same two tiles; tile height by the same round count
-        const int pp_mode = sizeof(T) == 2 ? sp_tune(SP_TUNE_CONV_PP, 1) : 0;
         if (pp_mode && fits30 && tall_mode <= 1) {
-            int th = (tall_ok && 19 * rt < 10 * rh) ? 16 : 8;
-            if (pp_mode == 8 || (pp_mode == 16 && tall_ok)) th = pp_mode;
+            int pp = (tall_ok && 19 * rt < 10 * rh) ? CK_PP_16ROW : CK_PP_8ROW;
+            if (pp_mode == 8 || (pp_mode == 16 && tall_ok)) pp = pp_mode == 16 ? CK_PP_16ROW : CK_PP_8ROW;
             // 16-row patches: conv_ppw.hip (64 co x 4 rows per wave, 0.25 LDS reads per MFMA under the ping-pong schedule) where its
             // epilogue covers the launch.  One of its items takes 1.72 - 2.04 x the time of an 8-row item (the longer K, the better: its
             // 128-value epilogue amortises; scratch/test_ppw.py, profiles/README.md) - it wins where the round count says so, and
             // everywhere the lockstep tall<2,16> kernel used to (8 - 15 % faster on the same tiles).  SP_TUNE_CONV_PPW: 0 off, 2 forced
             const int ppw_mode = sp_tune(SP_TUNE_CONV_PPW, 1);
-            if (tall_ok && ppw_mode && pp_mode == 1 && sp_conv_ppw_covers(p)) {
+            if (tall_ok && ppw_mode && pp_mode == 1 && (form = sp_conv_ppw_form(p)) >= 0) {
                 const int kch = (p.cin_p + 31) / 32;
                 const long ratio = kch >= 12 ? 172 : kch >= 6 ? 185 : kch >= 3 ? 194 : 204;
                 // (the 8-row form splits the items of a last, partial round along K - conv_pp.hip: its cost is no longer whole rounds)
@@ -1583,113 +1625,76 @@ int dispatch(const sp_conv_params& p, hipStream_t s) {
                 // takes a handful of launches the split 8-row form runs within 0 - 6 % of it (256 -> 256 @64^2 x 40: 138 vs 147 us, the
                 // others level) - step-neutral (profiles/round6_ab_ppw_tail_split_step.txt, round6_ab_ppw_pricing_step.txt), and ties
                 // go to the kernel that is measured, profiled and tuned as the dominant one
-                if (ppw_mode == 2 || ratio * rt < rh100) {                 // (ratio: per cent; rh100: hundredths of a round)
-                    const int rc = sp_conv_ppw_launch(p, s);
-                    if (rc != 1) return rc;
-                }
-                th = 8;             // where the four-row form loses on rounds, the 8-row ping-pong form beats the lockstep 16-row kernel too
+                if (ppw_mode == 2 || ratio * rt < rh100) return route(CK_PPW, form);      // (ratio: per cent; rh100: hundredths of a round)
+                pp = CK_PP_8ROW;    // where the four-row form loses on rounds, the 8-row ping-pong form beats the lockstep 16-row kernel too
             }
-            if (!(pp_mode == 1 && th == 16)) {             // (the 16-row form is reached only when forced: see conv_pp.hip)
-                const int rc = sp_conv_pp_launch(p, th, s);
-                if (rc != 1) return rc;
-            }
+            // (the 16-row form is reached only when forced: see conv_pp.hip)
+            if (!(pp_mode == 1 && pp == CK_PP_16ROW) && (form = sp_conv_pp_form(p, pp)) >= 0) return route(pp, form);
         }
         // a tall block does twice the work of a halo block in ~1.9x the time (scratch/bench_tall.py, profiles/README.md): it wins where
         // the round quantisation favours it (e.g. 160 instead of 320 blocks)
-        if (tall_ok && (tall_mode == 2 || 19 * rt < 10 * rh)) return launch_tall<T, 2>(p, s);
+        if (tall_ok && (tall_mode == 2 || 19 * rt < 10 * rh)) return route(CK_TALL_2_16);
         // remaining Cout > 64 layers: the 128 co x 8x32 tile on the LDS-DMA pipeline of the tall kernel (TH = 8; measured 74 ->
         // 67 us per launch in the step, 902 -> 914 img/s) or, with SP_CONV_SHORT=0 / tall_mode 0, on the register-staged halo kernel
-        const int short_env = sp_tune(SP_TUNE_CONV_SHORT, 1);
-        if (fits30 && (tall_mode == 3 || (tall_mode == 1 && short_env))) return launch_tall<T, 2, 8>(p, s);
-        return launch_halo<T, 128, 3>(p, s);
+        if (fits30 && (tall_mode == 3 || (tall_mode == 1 && sp_tune(SP_TUNE_CONV_SHORT, 1)))) return route(CK_TALL_2_8);
+        return route(CK_HALO_128);
     }
-    // 16-wide maps, Cout > 64, bf16: the ping-pong kernel on 16 x 16-pixel tiles (conv_pp.hip; SP_TUNE_CONV_PP = 0 or 2 keeps the
-    // LDS-DMA igemm below)
-    if (sizeof(T) == 2 && p.ksize == 3 && p.w_ == 16 && p.cout > 64) {
-        const int ppm = sp_tune(SP_TUNE_CONV_PP, 1);
-        if (ppm == 1 || ppm == 3) {
-            const int rc = sp_conv_pp_launch(p, 1616, s);
-            if (rc != 1) return rc;
-        }
-    }
-    // LDS-DMA kernel: measured faster for the small-spatial 3x3 layers (latency-bound), slower for 1x1 (profiles/README.md);
-    // SP_IGEMM_DMA=2 forces it everywhere, 0 disables it
-    const int dma_mode = sp_tune(SP_TUNE_IGEMM_DMA, 1);
-    if (p.cout > 16 && conv_operands_below_1g(p, sizeof(T)) && (dma_mode == 2 || (dma_mode == 1 && p.ksize == 3 && M <= 8192))) {
-        if (p.cout <= 32) return launch_dma<T, 1, 4, 2, 4>(p, s);        //  32 co x 256 px
-        if (p.cout <= 64) return launch_dma<T, 1, 4, 4, 4>(p, s);        //  64 co x 256 px
-        if (M <= 8192) {
-            switch (igemm_small_tile(M, p.cout, p.cin_p, p.ksize, p.dtype)) {
-                case 1: return launch_dma<T, 2, 2, 4, 4>(p, s);          // 128 co x 128 px
-                case 2: return launch_dma<T, 2, 2, 4, 2>(p, s);          // 128 co x  64 px
-                case 3: return launch_dma<T, 2, 2, 2, 4>(p, s);          //  64 co x 128 px
-                default: return launch_dma<T, 2, 2, 2, 2>(p, s);         //  64 co x  64 px
-            }
-        }
-        return launch_dma<T, 2, 2, 4, 4>(p, s);                          // 128 co x 128 px
-    }
-    if (p.cout <= 16) return launch_cfg<T, 1, 4, 1, 4>(p, s);            //  16 co x 256 px
-    if (p.cout <= 32) return launch_cfg<T, 1, 4, 2, 4>(p, s);            //  32 co x 256 px
-    if (p.cout <= 64) return launch_cfg<T, 1, 4, 4, 4>(p, s);            //  64 co x 256 px
-    if (M <= 8192) return launch_cfg<T, 2, 2, 2, 2>(p, s);               //  64 co x  64 px (tiny spatial: more blocks)
-    return launch_cfg<T, 2, 2, 4, 4>(p, s);                              // 128 co x 128 px
+    if (conv_w16_path(p.w_, p.cout, p.ksize, h16) && (form = sp_conv_pp_form(p, CK_PP_W16)) >= 0) return route(CK_PP_W16, form);
+    ConvRoute r = route(fits30 && conv_dma_path(M, p.cout, p.ksize) ? CK_IGEMM_DMA : CK_IGEMM);
+    const IgemmTile t = igemm_tile(r.kernel == CK_IGEMM_DMA, M, p.cout, p.cin_p, p.ksize, p.dtype);
+    r.co_t = t.co_t; r.px_t = t.px_t;
+    if (r.kernel == CK_IGEMM_DMA && (r.ksplit = igemm_ksplit(p, t)) > 1) r.form = CV_SPLITK;
+    return r;
 }
 
-}  // namespace
-
-extern "C" int sp_conv2d_workspace(int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ksize, int32_t dtype,
-                                   int64_t* bytes_out) {
-    SP_CHECK_ARG(bytes_out && n > 0 && h > 0 && w_ > 0 && cin_p > 0 && cout > 0 && (ksize == 1 || ksize == 3), "sp_conv2d_workspace: bad args");
-    *bytes_out = 0;
-    // mirrors dispatch(): only the LDS-DMA implicit GEMM (3x3, small spatial extent) splits K
-    const long M = (long)n * h * w_;
-    const int dma_mode = sp_tune(SP_TUNE_IGEMM_DMA, 1);
-    const bool halo_path = ksize == 3 && cout > 32 && h % HALO_TH == 0 && w_ % HALO_TW == 0;
-    const int kchunks = (cin_p + 31) / 32;
-    if (halo_path && dtype != SP_F32 && sp_tune(SP_TUNE_CONV_PP, 1)) {
-        // the ping-pong kernels' K-split of their last partial round (conv_pp.hip): partial tiles of the tail items, enough for
-        // whichever form dispatch() picks
-        const long b8 = std::max(tail_split_bytes(pp_items_8row(n, h, w_, cout), kchunks, SK_PP),
-                                 tail_split_bytes(pp_items_16row(n, h, w_, cout), kchunks, SK_PP));
-        *bytes_out = std::max(b8, tail_split_bytes(ppw_items(n, h, w_, cout), kchunks, SK_PPW));
-        return SP_OK;
+template <typename T>
+int dispatch(const sp_conv_params& p, const ConvRoute& r, hipStream_t s) {
+    const bool idx = r.form & CV_IDX;
+    switch (r.kernel) {
+        case CK_THINCO: return p.cin_p == 64 ? launch_thinco<2>(p, s) : launch_thinco<1>(p, s);
+        case CK_CIN8: return launch_cin8(p, s);
+        case CK_1X1_SPLITK: return launch_1x1_splitk(p, s);
+        case CK_1X1_DIRECT: return launch_1x1_direct(p, s);
+        case CK_HALO_64: return idx ? launch_halo<T, 64, 1, true>(p, s) : launch_halo<T, 64, 1>(p, s);
+        case CK_HALO_128: return launch_halo<T, 128, 3>(p, s);
+        case CK_TALL_1_16: return idx ? launch_tall<T, 1, 16, true>(p, s) : launch_tall<T, 1>(p, s);
+        case CK_TALL_2_16: return launch_tall<T, 2>(p, s);
+        case CK_TALL_2_8: return idx ? launch_tall<T, 2, 8, true>(p, s) : launch_tall<T, 2, 8>(p, s);
+        case CK_PP_8ROW: case CK_PP_16ROW: case CK_PP_W16: return sp_conv_pp_launch(p, r.kernel, s);
+        case CK_PPW: return sp_conv_ppw_launch(p, s);
+        case CK_IGEMM_DMA: switch (tile_key(r.co_t, r.px_t)) {
+            case tile_key(32, 256): return launch_dma<T, 1, 4, 2, 4>(p, r.ksplit, s);
+            case tile_key(64, 256): return launch_dma<T, 1, 4, 4, 4>(p, r.ksplit, s);
+            case tile_key(128, 128): return launch_dma<T, 2, 2, 4, 4>(p, r.ksplit, s);
+            case tile_key(128, 64): return launch_dma<T, 2, 2, 4, 2>(p, r.ksplit, s);
+            case tile_key(64, 128): return launch_dma<T, 2, 2, 2, 4>(p, r.ksplit, s);
+            case tile_key(64, 64): return launch_dma<T, 2, 2, 2, 2>(p, r.ksplit, s);
+        } break;
+        case CK_IGEMM: switch (tile_key(r.co_t, r.px_t)) {
+            case tile_key(16, 256): return launch_cfg<T, 1, 4, 1, 4>(p, s);
+            case tile_key(32, 256): return launch_cfg<T, 1, 4, 2, 4>(p, s);
+            case tile_key(64, 256): return launch_cfg<T, 1, 4, 4, 4>(p, s);
+            case tile_key(64, 64): return launch_cfg<T, 2, 2, 2, 2>(p, s);
+            case tile_key(128, 128): return launch_cfg<T, 2, 2, 4, 4>(p, s);
+        } break;
     }
-    if (ksize == 3 && w_ == 16 && cout > 64 && dtype != SP_F32 && (sp_tune(SP_TUNE_CONV_PP, 1) == 1 || sp_tune(SP_TUNE_CONV_PP, 1) == 3)) {
-        const long b16 = tail_split_bytes(pp_items_w16(n, h, w_, cout), kchunks, SK_PP);      // the same kernel on 16 x 16-pixel tiles
-        if (b16 > 0) { *bytes_out = b16; return SP_OK; }
-    }
-    if (ksize != 3 || halo_path || cout <= 16 || M > 8192 || dma_mode == 0) return SP_OK;
-    int co_t = cout <= 32 ? 32 : 64, px_t = cout <= 64 ? 256 : 64;
-    if (cout > 64) {                                                     // (the tile dispatch() picks for these layers)
-        const int tile = igemm_small_tile(M, cout, cin_p, ksize, dtype);
-        if (tile == 1 || tile == 2) co_t = 128;
-        if (tile == 1 || tile == 3) px_t = 128;
-    }
-    const int tiles = (int)((M + px_t - 1) / px_t) * ((cout + co_t - 1) / co_t);
-    const int e = dtype == SP_F32 ? 4 : 8;
-    const int nk = 9 * ((cin_p + 8 * e - 1) / (8 * e));
-    const int ksplit = split_k_plan(tiles, nk);
-    if (ksplit > 1) *bytes_out = (int64_t)ksplit * M * cout * 4;
-    return SP_OK;
+    sp_set_error(r.kernel == CK_UNSUPPORTED ? r.error : "sp_conv2d_igemm: no launcher for the planned route");
+    return SP_ERR_UNSUPPORTED;
 }
 
-extern "C" int sp_conv2d_igemm(const sp_conv_params* pp, sp_stream_t stream) {
-    SP_CHECK_ARG(pp != nullptr, "sp_conv2d_igemm: null params");
-    const sp_conv_params& p = *pp;
+// the argument checks of sp_conv2d_igemm / sp_conv2d_route (`pp` itself is checked by the caller)
+int conv_check_args(const sp_conv_params& p) {
     SP_CHECK_ARG(p.x && p.w && (p.y || (p.dtype == SP_F8 && p.y8) || (p.tail_w && p.tail_y)), "sp_conv2d_igemm: null tensor pointer");
     SP_CHECK_ARG(p.ksize == 1 || p.ksize == 3, "sp_conv2d_igemm: ksize %d unsupported (1 or 3)", p.ksize);
     SP_CHECK_ARG(p.n > 0 && p.h > 0 && p.w_ > 0 && p.cin_p > 0 && p.cout > 0, "sp_conv2d_igemm: bad dims");
     SP_CHECK_ARG(p.dtype == SP_F32 || p.dtype == SP_BF16 || p.dtype == SP_F8, "sp_conv2d_igemm: bad dtype %d", p.dtype);
     if (p.dtype == SP_F8) {
-        // BASELINE.json config 5: e4m3 operands on the fp8 MFMA, the ping-pong 3x3 kernel only (conv_pp.hip)
         SP_CHECK_ARG(p.x_scale && p.w_scale && (!p.y8 || p.y8_inv_scale), "sp_conv2d_igemm: SP_F8 needs x_scale, w_scale (and y8_inv_scale with y8)");
         SP_CHECK_ARG(p.cin_p % 16 == 0 && p.cout % 16 == 0 && p.ldy % 16 == 0 && p.ldy >= p.cout, "sp_conv2d_igemm: SP_F8 needs cin_p, cout, ldy multiples of 16");
         SP_CHECK_ARG(p.img_scale == nullptr, "sp_conv2d_igemm: SP_F8 does not take img_scale");
         SP_CHECK_ARG((p.act == SP_ACT_NONE || p.act == SP_ACT_RELU) && (p.pool2 == 0 || p.pool2 == 2) && !p.res1 && !p.res2 && !p.mask_src && !p.in_up2,
                      "sp_conv2d_igemm: SP_F8 supports act NONE / ReLU, pool2 0 / 2, no residuals, no mask_src, no in_up2");
-        const int rc = sp_conv_pp_launch(p, 8, reinterpret_cast<hipStream_t>(stream));
-        if (rc == 1) { sp_set_error("sp_conv2d_igemm: SP_F8 covers 3x3 layers with cout > 64, h %% 8 == 0, w %% 32 == 0 only"); return SP_ERR_UNSUPPORTED; }
-        return rc;
+        return SP_OK;
     }
     const int e = p.dtype == SP_F32 ? 4 : 8;
     SP_CHECK_ARG(p.cin_p % e == 0, "sp_conv2d_igemm: cin_p=%d must be a multiple of %d (16 bytes)", p.cin_p, e);
@@ -1707,25 +1712,57 @@ extern "C" int sp_conv2d_igemm(const sp_conv_params* pp, sp_stream_t stream) {
         SP_CHECK_ARG(p.ksize == 3 && p.cout > 32 && p.cout % 16 == 0 && p.h % HALO_TH == 0 && p.w_ % HALO_TW == 0 && p.ldy % 8 == 0 &&
                          p.mask_src == nullptr,
                      "sp_conv2d_igemm: pool2 needs a 3x3 layer with cout > 32, cout %% 16 == 0, h %% 8 == 0, w %% 32 == 0, ldy %% 8 == 0 and no mask_src");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (p.tail_w != nullptr) {
-        // fused 1x1 tail: the 64-channel FAST form of the ping-pong kernel only - no silent fall-back to a kernel that would ignore it
+    if (p.tail_w != nullptr)            // (the tail form takes no img_scale - conv_plan() - so img_split is not looked at)
         SP_CHECK_ARG(p.tail_y && p.tail_cout >= 1 && p.tail_cout <= 4 && p.tail_ld >= p.tail_cout && (p.tail_act == SP_ACT_NONE || p.tail_act == SP_ACT_TANH),
                      "sp_conv2d_igemm: bad tail arguments");
-        const bool ok = p.dtype == SP_BF16 && p.ksize == 3 && p.cout == 64 && p.h % 16 == 0 && p.w_ % 32 == 0 && (p.ldy & 7) == 0 && !p.pool2 &&
-                        !p.in_up2 && p.act != SP_ACT_TANH && p.img_scale == nullptr && sp_tune(SP_TUNE_CONV_PP, 1) && sp_tune(SP_TUNE_CONV_TALL, 1) == 1 &&
-                        !(sp_tune(SP_TUNE_CONV_PP_PRIO, 1) & 16);
-        if (!ok || sp_conv_pp_launch(p, 16, s) != SP_OK) {
-            sp_set_error("sp_conv2d_igemm: the fused 1x1 tail needs 16-bit storage, a 3x3 layer with cout == 64, h %% 16 == 0, w %% 32 == 0, ldy %% 8 == 0, no pooling");
-            return SP_ERR_UNSUPPORTED;
-        }
+    else if (p.img_scale != nullptr)
+        SP_CHECK_ARG(p.img_split >= 0 && p.img_split <= p.n, "sp_conv2d_igemm: img_split %d outside [0, n]", p.img_split);
+    return SP_OK;
+}
+
+}  // namespace
+
+extern "C" int sp_conv2d_workspace(int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ksize, int32_t dtype,
+                                   int64_t* bytes_out) {
+    SP_CHECK_ARG(bytes_out && n > 0 && h > 0 && w_ > 0 && cin_p > 0 && cout > 0 && (ksize == 1 || ksize == 3), "sp_conv2d_workspace: bad args");
+    *bytes_out = 0;
+    const long M = (long)n * h * w_;
+    const bool h16 = dtype != SP_F32, halo_path = conv_halo_path(M, h, w_, cin_p, cout, ksize);
+    const int kchunks = (cin_p + 31) / 32;
+    if (halo_path && h16 && sp_tune(SP_TUNE_CONV_PP, 1)) {
+        // the ping-pong kernels' K-split of their last partial round (conv_pp.hip): partial tiles of the tail items.  The maximum over
+        // the forms: which of them conv_plan() picks depends on the workspace lent, so the query cannot know it
+        const long b8 = std::max(tail_split_bytes(pp_items(CK_PP_8ROW, n, h, w_, cout), kchunks, SK_PP),
+                                 tail_split_bytes(pp_items(CK_PP_16ROW, n, h, w_, cout), kchunks, SK_PP));
+        *bytes_out = std::max(b8, tail_split_bytes(ppw_items(n, h, w_, cout), kchunks, SK_PPW));
         return SP_OK;
     }
-    if (p.img_scale != nullptr) {
-        SP_CHECK_ARG(p.img_split >= 0 && p.img_split <= p.n, "sp_conv2d_igemm: img_split %d outside [0, n]", p.img_split);
-        sp_conv_params q = p;                              // first output pixel of the second group (pooled geometry with pool2)
-        q.split_pix_ = (int64_t)p.img_split * (p.pool2 ? (long)(p.h / 2) * (p.w_ / 2) : (long)p.h * p.w_);
-        return q.dtype == SP_F32 ? dispatch<float>(q, s) : dispatch<bf16>(q, s);
+    if (conv_w16_path(w_, cout, ksize, h16)) {
+        const long b16 = tail_split_bytes(pp_items(CK_PP_W16, n, h, w_, cout), kchunks, SK_PP);      // the same kernel on 16 x 16-pixel tiles
+        if (b16 > 0) { *bytes_out = b16; return SP_OK; }
     }
-    return p.dtype == SP_F32 ? dispatch<float>(p, s) : dispatch<bf16>(p, s);
+    // only the LDS-DMA implicit GEMM on 3x3 layers of small spatial extent splits K
+    if (ksize != 3 || halo_path || M > 8192 || !conv_dma_path(M, cout, ksize)) return SP_OK;
+    const int ksplit = igemm_ksplit_wanted(igemm_tile(true, M, cout, cin_p, ksize, dtype), M, cout, cin_p, ksize, dtype);
+    if (ksplit > 1) *bytes_out = (int64_t)ksplit * M * cout * 4;
+    return SP_OK;
+}
+
+extern "C" int sp_conv2d_route(const sp_conv_params* pp, const char** route) {
+    SP_CHECK_ARG(pp != nullptr && route != nullptr, "sp_conv2d_route: null argument");
+    if (const int rc = conv_check_args(*pp)) return rc;
+    const ConvRoute r = conv_plan(*pp);
+    if (r.kernel == CK_UNSUPPORTED) { sp_set_error(r.error); return SP_ERR_UNSUPPORTED; }
+    *route = conv_route_name(r.kernel, r.form, pp->dtype == SP_F32);
+    return SP_OK;
+}
+
+extern "C" int sp_conv2d_igemm(const sp_conv_params* pp, sp_stream_t stream) {
+    SP_CHECK_ARG(pp != nullptr, "sp_conv2d_igemm: null params");
+    if (const int rc = conv_check_args(*pp)) return rc;
+    sp_conv_params p = *pp;
+    if (p.img_scale != nullptr)                            // first output pixel of the second group (pooled geometry with pool2)
+        p.split_pix_ = (int64_t)p.img_split * (p.pool2 ? (long)(p.h / 2) * (p.w_ / 2) : (long)p.h * p.w_);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return p.dtype == SP_F32 ? dispatch<float>(p, conv_plan(p), s) : dispatch<bf16>(p, conv_plan(p), s);
 }

@@ -765,11 +765,8 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(sp_conv_params p, int c
 template <typename T, int WCO, int PRIO, bool TIMING = false, bool DMA_IN_L = true, bool FAST = false, int FW = 2, bool TAIL = false, bool IDX = false>
 int launch_pp(const sp_conv_params& p, int prio, hipStream_t s) {
     using G = PPGeom<T, WCO, FW>;
-    // the form's admission on the dims and its work items (conv_common.h)
-    const long items = FW == 1 ? pp_items_w16(p.n, p.h, p.w_, p.cout) : WCO == 1 ? pp_items_16row(p.n, p.h, p.w_, p.cout)
-                                                                               : pp_items_8row(p.n, p.h, p.w_, p.cout);
-    if (items == 0) return 1;
-    const int total = (int)items;
+    constexpr int KERNEL = FW == 1 ? CK_PP_W16 : WCO == 1 ? CK_PP_16ROW : CK_PP_8ROW;
+    const int total = (int)pp_items(KERNEL, p.n, p.h, p.w_, p.cout);
     constexpr int LDS_BYTES = TAIL ? G::LDS_TAIL : G::LDS;
     static_assert(LDS_BYTES <= 163840, "LDS budget");
     constexpr auto kern = conv3x3_pp_kernel<T, WCO, PRIO, TIMING, DMA_IN_L, FAST, FW, TAIL, IDX>;
@@ -778,8 +775,7 @@ int launch_pp(const sp_conv_params& p, int prio, hipStream_t s) {
     // persistent: one block per CU; the items of a last, partial round split along K where the caller lent the scratch (top of the file)
     const TailSplit sk = tail_split_plan(total, (p.cin_p + G::KC - 1) / G::KC, SK_PP,
                                          (!G::F8 && !TIMING && !TAIL && p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0);
-    sp_note_route(G::F8 ? "conv3x3_pp<f8,2>" : FW == 1 ? "conv3x3_pp<16bit,2,FAST,w16>" : WCO == 2 ? (FAST ? "conv3x3_pp<16bit,2,FAST>" : "conv3x3_pp<16bit,2>")
-                                                                                  : (FAST ? "conv3x3_pp<16bit,1,FAST>" : "conv3x3_pp<16bit,1>"));
+    sp_note_route(conv_route_name(KERNEL, (G::F8 ? CV_F8 : 0) | (FAST ? CV_FAST : 0), false));
     hipLaunchKernelGGL(kern, dim3((unsigned)sk.grid), dim3(512), LDS_BYTES, s, p, cotiles, total, prio, tail_split_arg(sk));
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -787,44 +783,48 @@ int launch_pp(const sp_conv_params& p, int prio, hipStream_t s) {
 
 }  // namespace
 
-// conv_igemm.hip's dispatch(): bf16 3x3 layers with more than 64 output channels on (th x 32)-pixel patches, th = 8 or 16.
-// Returns 1 if the shape is not covered (the caller then keeps its own kernel).
-int sp_conv_pp_launch(const sp_conv_params& p, int th, hipStream_t s) {
-    if (p.dtype == SP_F8) {
-        if (p.ksize != 3 || !conv_operands_below_1g(p, 1) || (p.cout + 127) / 128 * 128 > PP_BIAS_MAX) return 1;
-        return launch_pp<f8, 2, 1>(p, 1, s);
-    }
-    if (p.dtype != SP_BF16 || p.ksize != 3 || !conv_operands_below_1g(p, 2)) return 1;
-    if (th == 1616) {
-        // maps 16 wide (th code 1616): 128 co x 16 x 16 px tiles - one whole image of the 16 x 16 layers per block.  Few items (80 for
-        // 512 -> 512 at batch 20), but each runs the ping-pong pipeline on a 128 x 256 tile instead of sixteen 64 x 64 tiles
-        // that re-read their operands from L2 (the LDS-DMA igemm these layers used): 512 -> 512: 53.4 -> 44.6 us, 520 -> 512: 70.8 ->
-        // 46.8, 256 -> 512: 29.0 -> 25.2; with 40 items (Cout 256) it is no faster - those stay on the igemm.  Split-K over 2-4 K
-        // ranges (fp32 partial tiles + the finalize pass) was built and measured: 60 us - a 128 x 256 fp32 tile per 12 stages is
-        // more store-path time than the extra parallelism buys
-        if (p.pool2 != 0 || (p.cout & 15) != 0 || (p.ldy & 7) != 0 || p.act == SP_ACT_TANH) return 1;
-        return launch_pp<bf16, 2, 1, false, true, true, 1>(p, 1, s);
-    }
-    if (th != 8 && th != 16) return 1;
+// The launch_pp instantiation that takes `p` on the items of `kernel` (conv_common.h: pp_items), as CV_* bits; -1: none does.
+int sp_conv_pp_form(const sp_conv_params& p, int kernel) {
+    if (p.ksize != 3 || pp_items(kernel, p.n, p.h, p.w_, p.cout) == 0) return -1;
+    if (p.dtype == SP_F8) return kernel == CK_PP_8ROW && conv_operands_below_1g(p, 1) && (p.cout + 127) / 128 * 128 <= PP_BIAS_MAX ? CV_F8 : -1;
+    if (p.dtype != SP_BF16 || !conv_operands_below_1g(p, 2)) return -1;
     // SP_TUNE_CONV_PP_PRIO (diagnostics / A-B): bit 2 = the TIMING build (bit 9 with it: stamps of mid-item chunks only),
     // bit 4 = the general epilogue everywhere
     const int prio = sp_tune(SP_TUNE_CONV_PP_PRIO, 1);
-    const bool fast = !(prio & 16) && p.pool2 == 0 && (p.cout & 15) == 0 && (p.ldy & 7) == 0 && p.act != SP_ACT_TANH;
-    if (p.tail_w != nullptr) {                             // the fused 1x1 tail: its own instantiation of the 64-channel FAST form
-        if (!(th == 16 && p.cout == 64 && fast)) return 1;
-        return launch_pp<bf16, 1, 1, false, true, true, 2, true>(p, prio, s);
-    }
-    if (p.pool_idx != nullptr) {                           // ReLU + MaxPool with recorded window positions: own instantiations (general epilogue)
-        if (p.pool2 != 2) return 1;
-        return th == 16 ? launch_pp<bf16, 1, 1, false, true, false, 2, false, true>(p, prio, s)
-                        : launch_pp<bf16, 2, 1, false, true, false, 2, false, true>(p, prio, s);
-    }
+    const bool fast_epi = p.pool2 == 0 && (p.cout & 15) == 0 && (p.ldy & 7) == 0 && p.act != SP_ACT_TANH, fast = fast_epi && !(prio & 16);
+    // maps 16 wide: 128 co x 16 x 16 px tiles - one whole image of the 16 x 16 layers per block.  Few items (80 for
+    // 512 -> 512 at batch 20), but each runs the ping-pong pipeline on a 128 x 256 tile instead of sixteen 64 x 64 tiles
+    // that re-read their operands from L2 (the LDS-DMA igemm these layers used): 512 -> 512: 53.4 -> 44.6 us, 520 -> 512: 70.8 ->
+    // 46.8, 256 -> 512: 29.0 -> 25.2; with 40 items (Cout 256) it is no faster - those stay on the igemm.  Split-K over 2-4 K
+    // ranges (fp32 partial tiles + the finalize pass) was built and measured: 60 us - a 128 x 256 fp32 tile per 12 stages is
+    // more store-path time than the extra parallelism buys
+    if (kernel == CK_PP_W16) return fast_epi ? CV_FAST : -1;
+    if (p.tail_w != nullptr) return kernel == CK_PP_16ROW && p.cout == 64 && fast ? (CV_TAIL | CV_FAST) : -1;     // the fused 1x1 tail: the 64-channel FAST form
+    if (p.pool_idx != nullptr) return p.pool2 == 2 ? CV_IDX : -1;      // ReLU + MaxPool with recorded window positions (general epilogue)
     // the TIMING build writes 256 x 8 x 16 floats of stamps into the caller's workspace: only with a workspace that holds them
-    const bool timing = (prio & 4) && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4;
-    if (th == 16) {                                        // 64 co x 16x32 px
-        if (timing && fast) return launch_pp<bf16, 1, 1, true, true, true>(p, prio, s);
-        return fast ? launch_pp<bf16, 1, 1, false, true, true>(p, prio, s) : launch_pp<bf16, 1, 1>(p, prio, s);
+    // (the 64-channel form has it with the FAST epilogue only)
+    const bool timing = (prio & 4) && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4 && (fast || kernel == CK_PP_8ROW);
+    return (fast ? CV_FAST : 0) | (timing ? CV_TIMING : 0);
+}
+
+int sp_conv_pp_launch(const sp_conv_params& p, int kernel, hipStream_t s) {
+    const int prio = sp_tune(SP_TUNE_CONV_PP_PRIO, 1), form = sp_conv_pp_form(p, kernel);
+    if (kernel == CK_PP_W16 && form == CV_FAST) return launch_pp<bf16, 2, 1, false, true, true, 1>(p, 1, s);
+    if (kernel == CK_PP_16ROW) switch (form) {             // 64 co x 16x32 px
+        case 0: return launch_pp<bf16, 1, 1>(p, prio, s);
+        case CV_FAST: return launch_pp<bf16, 1, 1, false, true, true>(p, prio, s);
+        case CV_FAST | CV_TIMING: return launch_pp<bf16, 1, 1, true, true, true>(p, prio, s);
+        case CV_FAST | CV_TAIL: return launch_pp<bf16, 1, 1, false, true, true, 2, true>(p, prio, s);
+        case CV_IDX: return launch_pp<bf16, 1, 1, false, true, false, 2, false, true>(p, prio, s);
     }
-    if (timing) return fast ? launch_pp<bf16, 2, 1, true, true, true>(p, prio, s) : launch_pp<bf16, 2, 1, true>(p, prio, s);
-    return fast ? launch_pp<bf16, 2, 1, false, true, true>(p, prio, s) : launch_pp<bf16, 2, 1>(p, prio, s);
+    if (kernel == CK_PP_8ROW) switch (form) {              // 128 co x 8x32 px
+        case 0: return launch_pp<bf16, 2, 1>(p, prio, s);
+        case CV_FAST: return launch_pp<bf16, 2, 1, false, true, true>(p, prio, s);
+        case CV_TIMING: return launch_pp<bf16, 2, 1, true>(p, prio, s);
+        case CV_FAST | CV_TIMING: return launch_pp<bf16, 2, 1, true, true, true>(p, prio, s);
+        case CV_IDX: return launch_pp<bf16, 2, 1, false, true, false, 2, false, true>(p, prio, s);
+        case CV_F8: return launch_pp<f8, 2, 1>(p, 1, s);
+    }
+    sp_set_error("sp_conv_pp_launch: no instantiation takes this launch (kernel %d, form %d)", kernel, form);
+    return SP_ERR_UNSUPPORTED;
 }

@@ -540,7 +540,7 @@ int launch_ppw(const sp_conv_params& p, int prio, hipStream_t s) {
     // persistent: one block per CU; the items of a last, partial round split along K where the caller lent the scratch
     const TailSplit sk = tail_split_plan(total, (p.cin_p + G::KC - 1) / G::KC, SK_PPW,
                                          (!TIMING && p.workspace != nullptr && p.split_sync != nullptr) ? p.workspace_bytes : 0);
-    sp_note_route("conv3x3_ppw<16bit> (64 co x 4 rows per wave)");
+    sp_note_route(conv_route_name(CK_PPW, 0, false));
     hipLaunchKernelGGL(kern, dim3((unsigned)sk.grid), dim3(512), G::LDS, s, p, cotiles, total, prio, tail_split_arg(sk));
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -548,18 +548,25 @@ int launch_ppw(const sp_conv_params& p, int prio, hipStream_t s) {
 
 }  // namespace
 
-// conv_igemm.hip's dispatch(): 16-bit 3x3 layers with more than 64 output channels on 16 x 32-pixel patches whose epilogue is the
-// FAST one.  Returns 1 if the shape is not covered (the caller then keeps its own kernel).
-int sp_conv_ppw_covers(const sp_conv_params& p) {
-    if (p.dtype != SP_BF16 || p.ksize != 3 || ppw_items(p.n, p.h, p.w_, p.cout) == 0 || !conv_operands_below_1g(p, 2)) return 0;
-    return !((p.cout & 15) != 0 || (p.ldy & 7) != 0 || p.act == SP_ACT_TANH || p.tail_w != nullptr || p.pool_idx != nullptr || p.y == nullptr);
+// conv_igemm.hip's conv_plan(): 16-bit 3x3 layers with more than 64 output channels on 16 x 32-pixel patches whose epilogue is the
+// FAST one.  The launch_ppw instantiation that takes `p`, as CV_* bits; -1: none does.
+int sp_conv_ppw_form(const sp_conv_params& p) {
+    if (p.dtype != SP_BF16 || p.ksize != 3 || ppw_items(p.n, p.h, p.w_, p.cout) == 0 || !conv_operands_below_1g(p, 2)) return -1;
+    if ((p.cout & 15) != 0 || (p.ldy & 7) != 0 || p.act == SP_ACT_TANH || p.tail_w != nullptr || p.pool_idx != nullptr || p.y == nullptr) return -1;
+    const int prio = sp_tune(SP_TUNE_CONV_PP_PRIO, 1);
+    if (p.pool2) return CV_POOL;
+    if ((prio & 4) && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4) return CV_TIMING;
+    return (prio & 64) ? CV_LA : 0;                        // (A/B: the requests in L_A, one behind every three reads)
 }
 
 int sp_conv_ppw_launch(const sp_conv_params& p, hipStream_t s) {
-    if (!sp_conv_ppw_covers(p)) return 1;
     const int prio = sp_tune(SP_TUNE_CONV_PP_PRIO, 1);
-    if (p.pool2) return launch_ppw<bf16, false, true, true>(p, prio, s);
-    if ((prio & 4) && p.workspace != nullptr && p.workspace_bytes >= 256L * 8 * 16 * 4) return launch_ppw<bf16, true>(p, prio, s);
-    if (prio & 64) return launch_ppw<bf16, false, false>(p, prio, s);      // (A/B: the requests in L_A, one behind every three reads)
-    return launch_ppw<bf16, false>(p, prio, s);
+    switch (sp_conv_ppw_form(p)) {
+        case 0: return launch_ppw<bf16, false>(p, prio, s);
+        case CV_POOL: return launch_ppw<bf16, false, true, true>(p, prio, s);
+        case CV_TIMING: return launch_ppw<bf16, true>(p, prio, s);
+        case CV_LA: return launch_ppw<bf16, false, false>(p, prio, s);
+    }
+    sp_set_error("sp_conv_ppw_launch: no instantiation takes this launch");
+    return SP_ERR_UNSUPPORTED;
 }

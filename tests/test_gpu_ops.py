@@ -500,6 +500,43 @@ def test_conv3x3_pingpong_four_row_waves_bf16(case):
         ops.set_tuning(TUNE_CONV_PP_SPLIT, -1)
 
 
+ROUTE_CASES = [  # (dtype, n, h, w, cin, cout, ksize, route) - one launch per kernel family, default knobs, the smallest shape it admits
+    (torch.bfloat16, 1, 8, 32, 32, 3, 3, "conv3x3_thinco"), (torch.bfloat16, 1, 16, 32, 8, 16, 3, "conv3x3_cin8"),
+    (torch.bfloat16, 1, 8, 8, 64, 64, 1, "conv1x1_direct"), (torch.bfloat16, 1, 8, 8, 128, 64, 1, "conv1x1_splitk"),
+    (torch.bfloat16, 1, 16, 32, 32, 64, 3, "conv3x3_pp<16bit,1,FAST>"), (torch.bfloat16, 1, 8, 32, 32, 80, 3, "conv3x3_pp<16bit,2,FAST>"),
+    # (the four-row-wave kernel wins on pricing only: 256 16-row items against two rounds of 8-row items, K of three chunks)
+    (torch.bfloat16, 8, 64, 64, 96, 512, 3, "conv3x3_ppw<16bit> (64 co x 4 rows per wave)"),
+    (torch.bfloat16, 32, 16, 16, 32, 256, 3, "conv3x3_pp<16bit,2,FAST,w16>"), (torch.bfloat16, 1, 8, 32, 32, 64, 3, "conv3x3_halo<16bit>"),
+    (torch.bfloat16, 1, 4, 4, 64, 32, 3, "conv_igemm_dma"), (torch.bfloat16, 1, 4, 4, 128, 32, 3, "conv_igemm_dma+finalize (split-K)"),
+    (torch.bfloat16, 1, 4, 4, 128, 16, 3, "conv_igemm (register-staged)"),
+    (torch.float32, 1, 16, 32, 8, 64, 3, "conv3x3_tall<f32,1,16>"), (torch.float32, 1, 8, 32, 8, 64, 3, "conv3x3_halo<f32>"),
+]
+
+
+def test_conv_route_query_names_the_kernel_that_runs(monkeypatch):
+    """sp_conv2d_route, asked with the very parameter block of a launch, names the kernel sp_last_route reports after it - one launch
+    per kernel family - and that kernel computes the convolution (fp32 arithmetic on the same operands)."""
+    planned = []
+    call = L.call
+
+    def spy(name, *args):
+        if name == "sp_conv2d_igemm":
+            planned.append(L.conv_route(args[0]._obj))
+        return call(name, *args)
+    monkeypatch.setattr(L, "call", spy)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    for dt, n, h, w_, cin, cout, k, want in ROUTE_CASES:
+        x = ops.nhwc_empty(n, cin, h, w_, dt, "cuda").normal_(generator=g)
+        w = (torch.randn(cout, k, k, cin, device="cuda", generator=g) * 0.05).to(dt)
+        y = ops.nhwc_empty(n, cout, h, w_, dt, "cuda").fill_(3.0)
+        ops._conv_launch(x, w.data_ptr(), None, y, None, None, None, 0.2, n, h, w_, cin, cout, cout, k, 0, dt)
+        got = L.lib().sp_last_route().decode()
+        assert planned[-1] == got == want, (want, planned[-1], got)
+        ref = F.conv2d(x.float(), w.float().permute(0, 3, 1, 2), None, padding=k // 2)
+        close(y, ref.cpu(), 8e-3 if dt == torch.bfloat16 else TOL[dt], want)
+    assert len(planned) == len(ROUTE_CASES)
+
+
 @pytest.mark.parametrize("case", [(20, 128, 512, 1, 0, False, True), (16, 520, 512, 0, 2, False, True), (32, 72, 256, 2, 0, True, False),
                                   (9, 64, 1024, 1, 1, False, True)])
 def test_conv3x3_pingpong_16_wide_tiles_bf16(case):
