@@ -211,8 +211,9 @@ int sp_conv2d_wgrad_accum(const void* x, const void* dy, float* dw, float* dbias
                           int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ld_dy, int32_t ksize,
                           int32_t dtype, sp_stream_t stream);
 /* sp_conv2d_wgrad_accum for a pool2 layer: dy is the gradient at the POOLED resolution [n][h/2][w/2][ld_dy] and stands for
- * 1/4 x its nearest-neighbour x2 expansion (n, h, w_ describe x).  Only the shapes of the row-walking kernel (bf16, 3x3,
- * w % 32 == 0, h % 2 == 0: sp_conv2d_wgrad_workspace() > 0); SP_ERR_INVALID otherwise. */
+ * 1/4 x its nearest-neighbour x2 expansion (n, h, w_ describe x).  Only what the row-walking kernel takes (bf16, 3x3, w % 32 == 0,
+ * h % 2 == 0, operands below 1 GiB; in the deterministic mode its slabs lent and at most 512 tile pairs): SP_ERR_INVALID otherwise.
+ * sp_conv2d_wgrad_route() with dy_pooled = 1 says beforehand which it is. */
 int sp_conv2d_wgrad_accum_pooled(const void* x, const void* dy, float* dw, float* dbias, float* workspace, int64_t workspace_floats,
                                  int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ld_dy, int32_t ksize,
                                  int32_t dtype, sp_stream_t stream);
@@ -227,6 +228,13 @@ int sp_conv2d_wgrad_workspace(int32_t n, int32_t h, int32_t w_, int32_t cin_p, i
 int sp_conv2d_wgrad_accum_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, float* workspace,
                                int64_t workspace_floats, int32_t n, int32_t split, int32_t h, int32_t w_, int32_t cin_p, int32_t cout,
                                int32_t ld_dy, int32_t ksize, int32_t dy_pooled, int32_t dtype, sp_stream_t stream);
+/* *route = the name sp_last_route() would report after the accumulating call with these arguments - split = 0 and dy_pooled = 0:
+ * sp_conv2d_wgrad_accum, dy_pooled != 0: sp_conv2d_wgrad_accum_pooled, split > 0: sp_conv2d_wgrad_accum_pair (where its two groups run one
+ * after the other: the second group's route) - without launching anything: same argument checks, same plan, same errors (an uncovered
+ * pooled shape: SP_ERR_INVALID).  Host-only: callable without a GPU.  want_dbias: the call is given a bias gradient to fill;
+ * workspace_floats: the scratch it is lent (0 = none). */
+int sp_conv2d_wgrad_route(int32_t n, int32_t split, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ld_dy, int32_t ksize,
+                          int32_t dy_pooled, int32_t want_dbias, int64_t workspace_floats, int32_t dtype, const char** route);
 /* Deferred slab reductions.  The streaming weight-gradient kernels of the 1x1 and 8-channel 3x3 layers split the pixels over blocks,
  * leave one partial tile per split in the workspace and a second, tiny launch adds the partial tiles to dW in a fixed order.  Nothing
  * reads dW before the end of a backward pass (model_wrapper.py:160,188: the optimizer step), so a caller may collect those launches:

@@ -144,6 +144,14 @@ def conv_route(p: SpConvParams) -> str:
     return out.value.decode()
 
 
+def wgrad_route(n, split, h, w, cin_p, cout, ld_dy, ksize, dy_pooled, want_dbias, workspace_floats, dtype) -> str:
+    """The kernel the accumulating weight-gradient call with these arguments would launch (include/sempyr.h: sp_conv2d_wgrad_route;
+    host-only); SempyrError with the library's message where it would fail."""
+    out = ctypes.c_char_p()
+    call("sp_conv2d_wgrad_route", n, split, h, w, cin_p, cout, ld_dy, ksize, int(dy_pooled), int(want_dbias), workspace_floats, dtype, ctypes.byref(out))
+    return out.value.decode()
+
+
 def call(name: str, *args) -> None:
     """Calls an int-returning entry point and raises SempyrError (with the library's message) on failure."""
     rc = getattr(lib(), name)(*args)

@@ -44,6 +44,16 @@ int main(void) {
                                 EXPECT(sp_conv2d_route(&q, &route) == SP_OK && route != NULL && strlen(route) > 0, "conv route");
                                 ++queries;
                             }
+                            // the weight gradient's route on the same shape: one group, pooled, two groups; with and without the scratch
+                            for (int form = 0; form < 3 && batches[b] > (form == 2); ++form)
+                                for (int lend = 0; lend < 2; ++lend) {
+                                    const char* route = NULL;
+                                    const int rc = sp_conv2d_wgrad_route(batches[b], form == 2 ? (batches[b] + 1) / 2 : 0, maps[m], maps[m], cin_p, chans[o], (chans[o] + e - 1) / e * e,
+                                                                         k, form == 1, lend, lend ? floats : 0, dt, &route);
+                                    if (form == 0) EXPECT(rc == SP_OK && route != NULL && strlen(route) > 0, "wgrad route");
+                                    else EXPECT(rc == SP_ERR_INVALID ? strlen(sp_last_error_string()) > 0 : (rc == SP_OK && route != NULL && strlen(route) > 0), "wgrad route (pooled / pair)");
+                                    ++queries;
+                                }
                             sp_set_tuning(SP_TUNE_DETERMINISTIC, -1);
                         }
     // argument-check failure paths of the launching entry points (they return before touching the device)
@@ -68,6 +78,18 @@ int main(void) {
     int64_t out;
     EXPECT(sp_conv2d_workspace(0, 8, 8, 8, 8, 3, SP_BF16, &out) == SP_ERR_INVALID, "workspace bad dims");
     EXPECT(sp_conv2d_wgrad_workspace(1, 8, 8, 8, 8, 2, SP_BF16, &out) == SP_ERR_INVALID, "wgrad workspace bad ksize");
+    EXPECT(sp_conv2d_wgrad_route(2, 0, 8, 32, 16, 16, 16, 3, 0, 0, 0, SP_BF16, NULL) == SP_ERR_INVALID, "wgrad route null");
+    EXPECT(sp_conv2d_wgrad_route(2, 2, 8, 32, 16, 16, 16, 3, 0, 0, 0, SP_BF16, &route) == SP_ERR_INVALID, "wgrad route split == n");
+    EXPECT(sp_conv2d_wgrad_route(2, 1, 8, 32, 12, 16, 16, 3, 0, 0, 0, SP_BF16, &route) == SP_ERR_INVALID, "wgrad route pair cin_p multiple");
+    EXPECT(sp_conv2d_wgrad_route(2, 0, 8, 32, 16, 16, 16, 5, 0, 0, 0, SP_BF16, &route) == SP_ERR_INVALID, "wgrad route ksize");
+    EXPECT(sp_conv2d_wgrad_route(2, 0, 8, 32, 16, 16, 16, 3, 0, 0, 0, 7, &route) == SP_ERR_INVALID, "wgrad route dtype");
+    EXPECT(sp_conv2d_wgrad_route(2, 0, 8, 32, 16, 24, 16, 3, 0, 0, 0, SP_BF16, &route) == SP_ERR_INVALID, "wgrad route cout > ld_dy");
+    EXPECT(sp_conv2d_wgrad_route(2, 0, 8, 32, 16, 16, 16, 3, 1, 0, 0, SP_F32, &route) == SP_ERR_INVALID, "wgrad route pooled fp32");
+    EXPECT(sp_conv2d_wgrad_route(2, 0, 8, 24, 16, 16, 16, 3, 1, 0, 0, SP_BF16, &route) == SP_ERR_INVALID, "wgrad route pooled w % 32");
+    EXPECT(sp_conv2d_wgrad_accum(NULL, NULL, NULL, NULL, NULL, 0, 2, 8, 32, 16, 16, 16, 3, SP_BF16, NULL) == SP_ERR_INVALID, "wgrad_accum null");
+    EXPECT(sp_conv2d_wgrad_accum_pair(&dummy, &dummy, (float*)&dummy, NULL, (float*)&dummy, NULL, NULL, 0, 2, 1, 8, 32, 12, 16, 16, 3, 0, SP_BF16, NULL) == SP_ERR_INVALID,
+           "wgrad_accum_pair cin_p multiple");
+    EXPECT(sp_conv2d_wgrad_accum_pooled(&dummy, &dummy, (float*)&dummy, NULL, NULL, 0, 2, 8, 24, 16, 16, 16, 3, SP_BF16, NULL) == SP_ERR_INVALID, "wgrad_accum_pooled w % 32");
     printf("asan_driver: %ld planner queries, %d failures\n", queries, fails);
     return fails != 0;
 }

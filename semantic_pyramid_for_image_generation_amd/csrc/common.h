@@ -193,21 +193,38 @@ int sp_conv_ppw_form(const sp_conv_params& p);                       // conv_ppw
 int sp_conv_ppw_launch(const sp_conv_params& p, hipStream_t s);
 // reduce_queue.hip (compiled once, shared by both flavours): true = the slab reduction was queued for sp_wgrad_reduce_flush
 bool spq_push_reduce(const float* slabs, int nsplit, long n_dw, float* dw, const float* bias_slabs, int bias_ld, int cout, float* dbias);
-// conv_wgrad_rows.hip: SP_OK after launching, 1 if the shape is not covered
-int sp_wgrad_rows_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout,
-                         int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s);
-long sp_wgrad_rows_workspace(int n, int h, int w, int cin, int cout);
-int sp_wgrad_rows_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split,
-                              int h, int w, int cin, int cout, int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s);
-// conv_wgrad_1x1.hip: same contract for the bf16 1x1 layers
-int sp_wgrad1x1_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout, int ld_dy,
-                       float* ws, long ws_floats, hipStream_t s);
-long sp_wgrad1x1_workspace(int n, int h, int w, int cin, int cout, int ld_dy);
-int sp_wgrad1x1_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h, int w,
-                            int cin, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s);
-int sp_wgrad3x3_cin8_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h,
-                                 int w, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s);
-// ... and for the 3x3 layers with an 8-channel input
-int sp_wgrad3x3_cin8_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cout, int ld_dy, float* ws,
-                            long ws_floats, hipStream_t s);
-long sp_wgrad3x3_cin8_workspace(int n, int h, int w, int cout, int ld_dy);
+// ---- The weight-gradient families (conv_wgrad_rows.hip, conv_wgrad_1x1.hip).  Each exports a PLAN - a pure host function of the dims,
+// the scratch lent and the tuning table; ok = false: the family does not take the layer - and a launcher for a plan that is ok
+// (dw_b != nullptr: the two groups of sp_conv2d_wgrad_accum_pair in one launch, a reduce pass per group).  conv_wgrad.hip's wgrad_plan()
+// chooses among them, its workspace query sizes the scratch from the same plans.
+enum WrForm { WR_ROWS_0, WR_ROWS_16, WR_ROWS_8, WR_PP3, WR_PP3_TIMING };
+// What one launch of the row walker does
+struct WrPlan {
+    bool ok;
+    WrForm form;
+    int pairs, ci_tiles;                     // (co, ci) tile pairs = grid.y
+    int blocks;                              // blocks per pair = grid.x = slabs per pair
+    int rows_per_block, rows_total;          // ping-pong form: block b walks the flattened image rows [b, b + 1) * rows_per_block
+    int rows_per_unit, units, thin_mode;     // 4-wave form: block b takes the units b, b + blocks, ... (thin_mode: WrArgs)
+    bool slabs, bias_part;                   // partial tiles / bias rows go to the slab area + reduce pass (false: fp32 atomics)
+    bool ordered;                            // deterministic mode: one fixed-order chain per element in the reduce pass
+    int kb;                                  // two groups: the first block of the second group
+};
+// split: 0 = one group; otherwise the images [0, split) and [split, n) accumulate into different gradients (two groups)
+WrPlan sp_wgrad_rows_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, int dy_up2, bool have_dbias, long ws_floats);
+long sp_wgrad_rows_workspace(int h, int w);          // scratch floats the plan of such a map wants lent
+int sp_wgrad_rows_launch(const WrPlan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int h, int w,
+                         int cin, int cout, int ld_dy, float* ws, int dy_up2, hipStream_t s);
+// the streaming kernels of the bf16 1x1 layers and of the 3x3 layers with an 8-channel input: one slab per pixel split
+struct W1Plan {
+    bool ok;
+    int tiles, ci_tiles, nsplit, stages_per_split;
+    int kb;                                  // two groups: the first split of the second group
+    long ws_need;                            // scratch floats of the slabs (0: a single split owns its dW rows)
+};
+W1Plan sp_wgrad1x1_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, long ws_floats);
+int sp_wgrad1x1_launch(const W1Plan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int h, int w,
+                       int cin, int cout, int ld_dy, float* ws, hipStream_t s);
+W1Plan sp_wgrad3x3_cin8_plan(int n, int split, int h, int w, int cout, int ld_dy, long ws_floats);
+int sp_wgrad3x3_cin8_launch(const W1Plan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int h, int w,
+                            int cout, int ld_dy, float* ws, hipStream_t s);

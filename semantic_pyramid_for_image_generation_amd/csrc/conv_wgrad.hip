@@ -13,6 +13,7 @@
 // Split-K over pixel ranges (grid.z = taps * nsplit).  The splits meet either through fp32 atomics on dW (throughput mode) or,
 // in the deterministic mode (SP_TUNE_DETERMINISTIC; default for fp32 storage), through one partial slab per split that an
 // ordered reduce pass sums (fp64) and adds to dW: bit-identical results run to run.
+#include <algorithm>
 #include <cstdlib>
 #include "common.h"
 
@@ -568,11 +569,44 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
-struct WgPlan { int nine; int nsplit; long per_split; };
+// ---- The weight gradient's route: which kernel an accumulating entry point launches.  wgrad_plan() decides it from the checked
+// arguments, the scratch lent and the tuning table without touching the device; wgrad_launch() launches it, sp_conv2d_wgrad_route()
+// reports it and sp_conv2d_wgrad_workspace() sizes the scratch from the same family plans.
+struct WgPlan { int nine; int nsplit; long per_split; int co_t, ci_t; bool slabs; };     // the per-tap kernels: split plan, tile, merge
+
+enum WgFamily { WG_CIN8, WG_ROWS, WG_1X1, WG_TAP9, WG_TAP };
+// one launch: the family and that family's plan.  two_groups: the launch covers both groups of a pair, one reduce pass per group
+struct WgLaunch { WgFamily family; bool two_groups, f32; WrPlan rows; W1Plan stream; WgPlan tap; };
+// launches = 1: one group, or both groups of a pair in one launch (l[0].two_groups); 2: the groups of a pair one after the other
+// (in_turn), each with its own route.  rc != SP_OK: unsupported, with its message - the group after the `launches` covered ones
+struct WgRoute { int launches; bool in_turn; WgLaunch l[2]; int rc; const char* error; };
+// the checked arguments of an entry point.  split: 0 = one group; dbias[g]: group g wants its bias gradient; fused: the w_packed / dot form
+struct WgArgs { int dtype, n, split, h, w, cin, cout, ld_dy, ksize, dy_pooled; bool dbias[2], fused; long ws_floats; };
+
+// sp_last_route() / sp_conv2d_wgrad_route(): the one place the names live - bench.py's route tables and the tests match on them
+const char* wgrad_route_name(const WgLaunch& l) {
+    switch (l.family) {
+        case WG_CIN8: return l.two_groups ? "wgrad3x3_cin8_stream (two groups) + 2 x reduce" : "wgrad3x3_cin8_stream + reduce";
+        case WG_1X1: return l.two_groups ? "wgrad1x1_stream (two groups) + 2 x reduce" : "wgrad1x1_stream + reduce";
+        case WG_ROWS:
+            switch (l.rows.form) {
+                case WR_ROWS_0: return "conv_wgrad_rows<0> + rows_reduce";
+                case WR_ROWS_16: return "conv_wgrad_rows<16> + rows_reduce";
+                case WR_ROWS_8: return "conv_wgrad_rows<8> + rows_reduce";
+                default: return l.two_groups ? "conv_wgrad_pp3 (row walker, ping-pong, two groups) + 2 x rows_reduce"
+                                             : "conv_wgrad_pp3 (row walker, ping-pong) + rows_reduce";
+            }
+        case WG_TAP9: return "conv_wgrad9 (per-tap, <= 64 channels)";
+        case WG_TAP: return l.f32 ? "conv_wgrad<f32> (per-tap)" : "conv_wgrad<16bit> (per-tap)";
+    }
+    return "";
+}
 
 template <typename T>
 WgPlan plan_wgrad(int n, int h, int w, int cin, int cout, int ksize, int co_t, int ci_t) {
-    WgPlan pl;
+    WgPlan pl = {};
+    pl.co_t = co_t;
+    pl.ci_t = ci_t;
     const long M = (long)n * h * w;
     pl.nine = (ksize == 3 && w % Wg9Traits<T>::PXS == 0 && cin >= 16 && cin <= 64 && cout <= 64) ? 1 : 0;
     if (pl.nine) {
@@ -606,9 +640,113 @@ WgPlan plan_wgrad(int n, int h, int w, int cin, int cout, int ksize, int co_t, i
     return pl;
 }
 
-inline void wgrad_tile(int cin, int cout, int& co_t, int& ci_t) {
-    co_t = cout <= 64 ? 64 : 128;
-    ci_t = cin <= 64 ? 64 : 128;
+// tile shape + split plan of the per-tap kernels for one layer
+template <typename T>
+WgPlan pertap_plan(int n, int h, int w, int cin, int cout, int ksize) {
+    int co_t = cout <= 64 ? 64 : 128, ci_t = cin <= 64 ? 64 : 128;
+    // tiny pixel counts (8x8, 4x4 maps): the operands live in L2, so 64 x 64 tiles cost nothing extra and give enough blocks
+    // without a K split - no merge at all (SP_TUNE_WGRAD_SMALL_M, default 2048 pixels)
+    const long small_m = sp_tune(SP_TUNE_WGRAD_SMALL_M, 2048);
+    // 1x1 layers: dW is at most 256 x 256, so 64 x 64 tiles quadruple the tile count and shorten every merge
+    const int k1_small = sp_tune(SP_TUNE_WGRAD_K1_TILE64, 1);
+    if ((long)n * h * w <= small_m || (ksize == 1 && k1_small)) co_t = ci_t = 64;
+    return plan_wgrad<T>(n, h, w, cin, cout, ksize, co_t, ci_t);
+}
+
+// fp32 scratch (floats) the deterministic merge of the per-tap kernels needs: one dW slab + one bias row per split
+long pertap_slab_floats(const WgPlan& pl, int cin, int cout, int ksize) {
+    return pl.nsplit <= 1 ? 0 : (long)pl.nsplit * ((long)cout * ksize * ksize * cin + ((cout + 3) & ~3));
+}
+
+// the per-tap kernels with their merge: throughput mode keeps the atomics (the slab mode measured slower); deterministic mode: every
+// split stores its partial tile (and bias row) with plain stores and a second pass sums them in split order - or, without (enough)
+// scratch (sp_conv2d_wgrad has no workspace argument, the others document it as optional), ONE split per tile, which then owns its dW
+// rows (ordered, no merge; slower than the split plan)
+template <typename T>
+WgPlan pertap_route(const WgArgs& a, int n) {
+    WgPlan pl = pertap_plan<T>(n, a.h, a.w, a.cin, a.cout, a.ksize);
+    const long n_dw = (long)a.cout * a.ksize * a.ksize * a.cin;
+    const bool det = sp_deterministic(a.dtype);
+    pl.slabs = det && pl.nsplit > 1 && a.ws_floats >= pertap_slab_floats(pl, a.cin, a.cout, a.ksize) && (n_dw & 3) == 0;
+    if (det && pl.nsplit > 1 && !pl.slabs) {
+        const long M = (long)n * a.h * a.w;
+        pl.nsplit = 1;
+        pl.per_split = pl.nine ? (long)n * a.h * (a.w / Wg9Traits<T>::PXS) : ((M + WgTraits<T>::PK - 1) / WgTraits<T>::PK) * WgTraits<T>::PK;
+    }
+    return pl;
+}
+
+// one group of n images (dbias: it wants its bias gradient); false = no kernel covers it (only a pooled gradient can be left out)
+bool wgrad_plan_group(const WgArgs& a, int n, bool dbias, WgLaunch& l) {
+    const bool b16 = a.dtype == SP_BF16;
+    l = {};
+    l.f32 = !b16;
+    if (a.dy_pooled) {
+        // the gradient of a fused 2x2 average pooling at the pooled resolution: only the row walker reads it
+        l.family = WG_ROWS;
+        l.rows = sp_wgrad_rows_plan(n, 0, a.h, a.w, a.cin, a.cout, a.ld_dy, 1, dbias, a.ws_floats);
+        return l.rows.ok;
+    }
+    if (b16 && !a.fused && a.ksize == 3) {
+        if (a.cin == 8) {
+            // the padded RGB images: streaming kernel with an im2col X tile (conv_wgrad_1x1.hip)
+            l.family = WG_CIN8;
+            l.stream = sp_wgrad3x3_cin8_plan(n, 0, a.h, a.w, a.cout, a.ld_dy, a.ws_floats);
+            if (l.stream.ok) return true;
+        }
+        if (sp_tune(SP_TUNE_WGRAD_ROWS, 1)) {
+            // row-walker kernel (conv_wgrad_rows.hip): all nine taps per block, 4.4x fewer L2 bytes per flop
+            l.family = WG_ROWS;
+            l.rows = sp_wgrad_rows_plan(n, 0, a.h, a.w, a.cin, a.cout, a.ld_dy, 0, dbias, a.ws_floats);
+            if (l.rows.ok) return true;
+        }
+    }
+    if (b16 && !a.fused && a.ksize == 1) {
+        // streaming kernel of the 1x1 layers (conv_wgrad_1x1.hip): long-lived blocks, LDS-DMA ring, slabs + ordered reduce
+        l.family = WG_1X1;
+        l.stream = sp_wgrad1x1_plan(n, 0, a.h, a.w, a.cin, a.cout, a.ld_dy, a.ws_floats);
+        if (l.stream.ok) return true;
+    }
+    l.tap = b16 ? pertap_route<bf16>(a, n) : pertap_route<float>(a, n);
+    l.family = l.tap.nine ? WG_TAP9 : WG_TAP;
+    return true;
+}
+
+WgRoute wgrad_plan(const WgArgs& a) {
+    WgRoute r = {};
+    const bool b16 = a.dtype == SP_BF16;
+    r.launches = 1;
+    WgLaunch& l = r.l[0];
+    if (a.split > 0 && a.dbias[0] == a.dbias[1] && b16) {
+        // two groups in ONE launch where the group boundary falls between two blocks (row walker) or two splits (streaming kernels)
+        l.two_groups = true;
+        if (a.ksize == 3 && a.cin == 8 && !a.dy_pooled) {
+            l.family = WG_CIN8;
+            l.stream = sp_wgrad3x3_cin8_plan(a.n, a.split, a.h, a.w, a.cout, a.ld_dy, a.ws_floats);
+            if (l.stream.ok) return r;
+        }
+        if (a.ksize == 3 && a.cin != 8 && sp_tune(SP_TUNE_WGRAD_ROWS, 1)) {
+            l.family = WG_ROWS;
+            l.rows = sp_wgrad_rows_plan(a.n, a.split, a.h, a.w, a.cin, a.cout, a.ld_dy, a.dy_pooled ? 1 : 0, a.dbias[0], a.ws_floats);
+            if (l.rows.ok) return r;
+        }
+        if (a.ksize == 1 && !a.dy_pooled) {
+            l.family = WG_1X1;
+            l.stream = sp_wgrad1x1_plan(a.n, a.split, a.h, a.w, a.cin, a.cout, a.ld_dy, a.ws_floats);
+            if (l.stream.ok) return r;
+        }
+    }
+    // one group - or everything else: the two groups one after the other (contiguous image ranges)
+    r.in_turn = a.split > 0;
+    for (r.launches = 0; r.launches < (r.in_turn ? 2 : 1); ++r.launches) {
+        const int g = r.launches, ng = r.in_turn ? (g ? a.n - a.split : a.split) : a.n;
+        if (!wgrad_plan_group(a, ng, a.dbias[g], r.l[g])) {
+            r.rc = SP_ERR_INVALID;
+            r.error = "sp_conv2d_wgrad_accum_pooled: shape not covered by the row-walking kernel (w % 32, h % 2)";
+            break;
+        }
+    }
+    return r;
 }
 
 template <typename T>
@@ -620,7 +758,6 @@ int launch_wgrad9(const T* x, const T* dy, float* dw, int n, int h, int w, int c
     if (const int rc = sp_lds_limit<kern>(LDS)) return rc;
     const long n_dw = (long)cout * 9 * cin;
     dim3 grid(sp_div_up(cin, 64), sp_div_up(cout, 64), (unsigned)pl.nsplit);
-    sp_note_route("conv_wgrad9 (per-tap, <= 64 channels)");
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, x, dy, dw, n, h, w, cin, cout, ld_dy, (int)pl.per_split, dbias, w_packed, dot, slabs, n_dw,
                        bias_slabs, bias_ld);
     SP_LAUNCH_CHECK();
@@ -638,81 +775,33 @@ int launch_wgrad(const T* x, const T* dy, float* dw, int n, int h, int w, int ci
     const int taps = ksize * ksize;
     const long n_dw = (long)cout * taps * cin;
     dim3 grid(sp_div_up(cin, CI_T), sp_div_up(cout, CO_T), taps * pl.nsplit);
-    sp_note_route(sizeof(T) == 4 ? "conv_wgrad<f32> (per-tap)" : "conv_wgrad<16bit> (per-tap)");
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, x, dy, dw, n, h, w, cin, cout, ld_dy, ksize, pl.nsplit, pl.per_split, dbias, w_packed, dot,
                        slabs, n_dw, bias_slabs, bias_ld);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
 
-// tile shape + split plan of the per-tap kernels for one layer (shared by the dispatcher and the workspace query)
-template <typename T>
-WgPlan pertap_plan(int n, int h, int w, int cin, int cout, int ksize, int& co_t, int& ci_t) {
-    wgrad_tile(cin, cout, co_t, ci_t);
-    // tiny pixel counts (8x8, 4x4 maps): the operands live in L2, so 64 x 64 tiles cost nothing extra and give enough blocks
-    // without a K split - no merge at all (SP_TUNE_WGRAD_SMALL_M, default 2048 pixels)
-    const long small_m = sp_tune(SP_TUNE_WGRAD_SMALL_M, 2048);
-    // 1x1 layers: dW is at most 256 x 256, so 64 x 64 tiles quadruple the tile count and shorten every merge
-    const int k1_small = sp_tune(SP_TUNE_WGRAD_K1_TILE64, 1);
-    if ((long)n * h * w <= small_m || (ksize == 1 && k1_small)) co_t = ci_t = 64;
-    return plan_wgrad<T>(n, h, w, cin, cout, ksize, co_t, ci_t);
-}
+// the pointers of one launch: (dw_b, dbias_b) belong to the second group of a two-group launch
+struct WgPtrs { const void* x; const void* dy; float* dw; float* dbias; float* dw_b; float* dbias_b; const void* w_packed; float* dot; float* ws; };
 
-// fp32 scratch (floats) the deterministic merge of this layer needs: one dW slab + one bias row per split
+// a per-tap kernel + the reduce pass of its slabs
 template <typename T>
-long pertap_slab_floats(int n, int h, int w, int cin, int cout, int ksize) {
-    int co_t, ci_t;
-    const WgPlan pl = pertap_plan<T>(n, h, w, cin, cout, ksize, co_t, ci_t);
-    if (pl.nsplit <= 1) return 0;
-    return (long)pl.nsplit * ((long)cout * ksize * ksize * cin + ((cout + 3) & ~3));
-}
-
-template <typename T>
-int dispatch_wgrad(const void* x, const void* dy, float* dw, int n, int h, int w, int cin, int cout, int ld_dy,
-                   int ksize, float* dbias, const void* w_packed, float* dot, float* ws, long ws_floats, hipStream_t s) {
-    const T* xt = reinterpret_cast<const T*>(x);
-    const T* dt = reinterpret_cast<const T*>(dy);
-    const T* wpk = reinterpret_cast<const T*>(w_packed);
-    const bool det = sp_deterministic(sizeof(T) == 2 ? SP_BF16 : SP_F32);
-    if (sizeof(T) == 2 && ksize == 3 && cin == 8 && w_packed == nullptr && dot == nullptr) {
-        // the padded RGB images: streaming kernel with an im2col X tile (conv_wgrad_1x1.hip)
-        const int rc = sp_wgrad3x3_cin8_launch(x, dy, dw, dbias, n, h, w, cout, ld_dy, ws, ws_floats, s);
-        if (rc != 1) return rc;
-    }
-    if (sizeof(T) == 2 && ksize == 3 && w_packed == nullptr && dot == nullptr) {
-        // row-walker kernel (conv_wgrad_rows.hip): all nine taps per block, 4.4x fewer L2 bytes per flop
-        if (sp_tune(SP_TUNE_WGRAD_ROWS, 1)) {
-            const int rc = sp_wgrad_rows_launch(x, dy, dw, dbias, n, h, w, cin, cout, ld_dy, ws, ws_floats, 0, s);
-            if (rc != 1) return rc;
-        }
-    }
-    if (sizeof(T) == 2 && ksize == 1 && w_packed == nullptr && dot == nullptr) {
-        // streaming kernel of the 1x1 layers (conv_wgrad_1x1.hip): long-lived blocks, LDS-DMA ring, slabs + ordered reduce
-        const int rc = sp_wgrad1x1_launch(x, dy, dw, dbias, n, h, w, cin, cout, ld_dy, ws, ws_floats, s);
-        if (rc != 1) return rc;
-    }
-    // throughput mode: the per-tap kernels keep their atomics (their slab mode measured slower); deterministic mode: slabs
-    if (!det) { ws = nullptr; ws_floats = 0; }
-    int co_t, ci_t;
-    WgPlan pl = pertap_plan<T>(n, h, w, cin, cout, ksize, co_t, ci_t);
+int launch_pertap(const WgPlan& pl, const WgPtrs& p, int n, int h, int w, int cin, int cout, int ld_dy, int ksize, hipStream_t s) {
+    const T* xt = reinterpret_cast<const T*>(p.x);
+    const T* dt = reinterpret_cast<const T*>(p.dy);
+    const T* wpk = reinterpret_cast<const T*>(p.w_packed);
+    float* dw = p.dw;
+    float* dbias = p.dbias;
+    float* dot = p.dot;
     const long n_dw = (long)cout * ksize * ksize * cin;
     const int bias_ld = (cout + 3) & ~3;
-    // slab mode: every split stores its partial tile (and bias row) with plain stores and a second pass sums them in split
-    // order; without it the splits meet through fp32 atomics.  A single split owns its dW rows: no merge either way.
-    float* slabs = (ws != nullptr && pl.nsplit > 1 && ws_floats >= (long)pl.nsplit * (n_dw + bias_ld) && (n_dw & 3) == 0) ? ws : nullptr;
-    if (det && pl.nsplit > 1 && slabs == nullptr) {
-        // deterministic mode without (enough) scratch - sp_conv2d_wgrad has no workspace argument, the others document it as
-        // optional: ONE split per tile, which then owns its dW rows (ordered, no merge; slower than the split plan)
-        const long M = (long)n * h * w;
-        pl.nsplit = 1;
-        pl.per_split = pl.nine ? (long)n * h * (w / Wg9Traits<T>::PXS) : ((M + WgTraits<T>::PK - 1) / WgTraits<T>::PK) * WgTraits<T>::PK;
-    }
+    float* slabs = pl.slabs ? p.ws : nullptr;
     float* bias_slabs = (slabs != nullptr && dbias != nullptr) ? slabs + (long)pl.nsplit * n_dw : nullptr;
     int rc;
     if (pl.nine) rc = launch_wgrad9<T>(xt, dt, dw, n, h, w, cin, cout, ld_dy, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
-    else if (co_t == 64 && ci_t == 64) rc = launch_wgrad<T, 2, 2>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
-    else if (co_t == 64) rc = launch_wgrad<T, 2, 4>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
-    else if (ci_t == 64) rc = launch_wgrad<T, 4, 2>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
+    else if (pl.co_t == 64 && pl.ci_t == 64) rc = launch_wgrad<T, 2, 2>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
+    else if (pl.co_t == 64) rc = launch_wgrad<T, 2, 4>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
+    else if (pl.ci_t == 64) rc = launch_wgrad<T, 4, 2>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
     else rc = launch_wgrad<T, 4, 4>(xt, dt, dw, n, h, w, cin, cout, ld_dy, ksize, dbias, wpk, dot, slabs, bias_slabs, bias_ld, pl, s);
     if (rc != SP_OK || slabs == nullptr) return rc;
     long blocks = (n_dw / 4 + 255) / 256;
@@ -723,65 +812,98 @@ int dispatch_wgrad(const void* x, const void* dy, float* dw, int n, int h, int w
     return SP_OK;
 }
 
-}  // namespace
+// one launch over the n images from p.x / p.dy on
+int wgrad_launch(const WgLaunch& l, const WgArgs& a, const WgPtrs& p, int n, hipStream_t s) {
+    sp_note_route(wgrad_route_name(l));
+    switch (l.family) {
+        case WG_CIN8: return sp_wgrad3x3_cin8_launch(l.stream, p.x, p.dy, p.dw, p.dbias, p.dw_b, p.dbias_b, n, a.h, a.w, a.cout, a.ld_dy, p.ws, s);
+        case WG_1X1: return sp_wgrad1x1_launch(l.stream, p.x, p.dy, p.dw, p.dbias, p.dw_b, p.dbias_b, n, a.h, a.w, a.cin, a.cout, a.ld_dy, p.ws, s);
+        case WG_ROWS: return sp_wgrad_rows_launch(l.rows, p.x, p.dy, p.dw, p.dbias, p.dw_b, p.dbias_b, n, a.h, a.w, a.cin, a.cout, a.ld_dy, p.ws, a.dy_pooled ? 1 : 0, s);
+        case WG_TAP9:
+        case WG_TAP: break;
+    }
+    return l.f32 ? launch_pertap<float>(l.tap, p, n, a.h, a.w, a.cin, a.cout, a.ld_dy, a.ksize, s)
+                 : launch_pertap<bf16>(l.tap, p, n, a.h, a.w, a.cin, a.cout, a.ld_dy, a.ksize, s);
+}
 
-extern "C" int sp_conv2d_wgrad_accum_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b,
-                                          float* workspace, int64_t workspace_floats, int32_t n, int32_t split, int32_t h, int32_t w_,
-                                          int32_t cin_p, int32_t cout, int32_t ld_dy, int32_t ksize, int32_t dy_pooled, int32_t dtype,
-                                          sp_stream_t stream) {
-    SP_CHECK_ARG(x && dy && dw_a && dw_b && split > 0 && split < n, "sp_conv2d_wgrad_accum_pair: bad args");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == SP_BF16 && ksize == 3 && cin_p == 8 && !dy_pooled) {
-        // the padded RGB images: the streaming kernel, one launch over both groups + a reduce pass per group
-        const int rc = sp_wgrad3x3_cin8_launch_pair(x, dy, dw_a, dbias_a, dw_b, dbias_b, n, split, h, w_, cout, ld_dy, workspace, workspace_floats, s);
-        if (rc != 1) return rc;
-    }
-    if (dtype == SP_BF16 && ksize == 3 && cin_p != 8 && sp_tune(SP_TUNE_WGRAD_ROWS, 1)) {
-        // one launch of the row walker over both groups where the group boundary falls between two of its blocks
-        const int rc = sp_wgrad_rows_launch_pair(x, dy, dw_a, dbias_a, dw_b, dbias_b, n, split, h, w_, cin_p, cout, ld_dy, workspace, workspace_floats,
-                                                 dy_pooled ? 1 : 0, s);
-        if (rc != 1) return rc;
-    }
-    if (dtype == SP_BF16 && ksize == 1 && !dy_pooled) {
-        const int rc = sp_wgrad1x1_launch_pair(x, dy, dw_a, dbias_a, dw_b, dbias_b, n, split, h, w_, cin_p, cout, ld_dy, workspace, workspace_floats, s);
-        if (rc != 1) return rc;
-    }
-    // everything else: the two groups one after the other (contiguous image ranges)
-    const long esz = dtype == SP_F32 ? 4 : 2;
-    const long xs = (long)h * w_ * cin_p * esz;
-    const long ds = (dy_pooled ? (long)(h / 2) * (w_ / 2) : (long)h * w_) * ld_dy * esz;
-    for (int g = 0; g < 2; ++g) {
-        const int n0 = g ? split : 0, ng = g ? n - split : split;
-        const char* xg = reinterpret_cast<const char*>(x) + n0 * xs;
-        const char* dg = reinterpret_cast<const char*>(dy) + n0 * ds;
-        const int rc = dy_pooled ? sp_conv2d_wgrad_accum_pooled(xg, dg, g ? dw_b : dw_a, g ? dbias_b : dbias_a, workspace, workspace_floats, ng, h, w_,
-                                                                cin_p, cout, ld_dy, ksize, dtype, stream)
-                                 : sp_conv2d_wgrad_accum(xg, dg, g ? dw_b : dw_a, g ? dbias_b : dbias_a, workspace, workspace_floats, ng, h, w_, cin_p, cout,
-                                                         ld_dy, ksize, dtype, stream);
-        if (rc != SP_OK) return rc;
-    }
+// The argument checks of every accumulating entry point and of the route query (p == nullptr: it has no pointers); `who` keeps each
+// message's own prefix.
+int wgrad_check(const char* who, const WgArgs& a, const WgPtrs* p) {
+    SP_CHECK_ARG(p == nullptr || (p->x && p->dy && p->dw && (a.split == 0 || p->dw_b)), "%s: null pointer", who);
+    if (a.dy_pooled) SP_CHECK_ARG(a.ksize == 3 && a.dtype == SP_BF16, "%s: bf16 3x3 layers only", who);
+    SP_CHECK_ARG(a.ksize == 1 || a.ksize == 3, "%s: ksize %d unsupported", who, a.ksize);
+    SP_CHECK_ARG(a.dtype == SP_F32 || a.dtype == SP_BF16, "%s: bad dtype %d", who, a.dtype);
+    const int e = a.dtype == SP_F32 ? 4 : 8;
+    SP_CHECK_ARG(a.cin % e == 0 && a.ld_dy % e == 0, "%s: cin_p=%d and ld_dy=%d must be multiples of %d", who, a.cin, a.ld_dy, e);
+    SP_CHECK_ARG(a.n > 0 && a.h > 0 && a.w > 0 && a.cout > 0 && a.cout <= a.ld_dy && (!a.dy_pooled || (a.h % 2 == 0 && a.w % 2 == 0)), "%s: bad dims", who);
     return SP_OK;
 }
 
+// plan -> launch(es), for all four accumulating entry points (after wgrad_check)
+int wgrad_run(const WgArgs& a, const WgPtrs& p, sp_stream_t stream) {
+    const WgRoute r = wgrad_plan(a);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long esz = a.dtype == SP_F32 ? 4 : 2;
+    const long xs = (long)a.h * a.w * a.cin * esz;
+    const long ds = (a.dy_pooled ? (long)(a.h / 2) * (a.w / 2) : (long)a.h * a.w) * a.ld_dy * esz;
+    if (!r.in_turn && r.launches == 1) return wgrad_launch(r.l[0], a, p, a.n, s);
+    for (int g = 0; g < r.launches; ++g) {
+        const int n0 = g ? a.split : 0, ng = g ? a.n - a.split : a.split;
+        const WgPtrs pg = {reinterpret_cast<const char*>(p.x) + n0 * xs, reinterpret_cast<const char*>(p.dy) + n0 * ds, g ? p.dw_b : p.dw,
+                           g ? p.dbias_b : p.dbias, nullptr, nullptr, nullptr, nullptr, p.ws};
+        if (const int rc = wgrad_launch(r.l[g], a, pg, ng, s)) return rc;
+    }
+    // (a pair whose second group alone is uncovered has launched its first group by now, as it always has)
+    if (r.rc != SP_OK) sp_set_error("%s", r.error);
+    return r.rc;
+}
+
+}  // namespace
+
+extern "C" int sp_conv2d_wgrad_route(int32_t n, int32_t split, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ld_dy, int32_t ksize,
+                                     int32_t dy_pooled, int32_t want_dbias, int64_t workspace_floats, int32_t dtype, const char** route) {
+    SP_CHECK_ARG(route != nullptr, "sp_conv2d_wgrad_route: null argument");
+    SP_CHECK_ARG(split == 0 || (split > 0 && split < n), "sp_conv2d_wgrad_accum_pair: bad args");
+    const WgArgs a = {dtype, n, split, h, w_, cin_p, cout, ld_dy, ksize, dy_pooled, {want_dbias != 0, want_dbias != 0}, false, workspace_floats};
+    if (const int rc = wgrad_check(split ? "sp_conv2d_wgrad_accum_pair" : dy_pooled ? "sp_conv2d_wgrad_accum_pooled" : "sp_conv2d_wgrad_accum", a, nullptr)) return rc;
+    const WgRoute r = wgrad_plan(a);
+    if (r.rc != SP_OK) { sp_set_error("%s", r.error); return r.rc; }
+    *route = wgrad_route_name(r.l[r.launches - 1]);
+    return SP_OK;
+}
+
+extern "C" int sp_conv2d_wgrad_accum_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, float* workspace,
+                                          int64_t workspace_floats, int32_t n, int32_t split, int32_t h, int32_t w_, int32_t cin_p, int32_t cout,
+                                          int32_t ld_dy, int32_t ksize, int32_t dy_pooled, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(x && dy && dw_a && dw_b && split > 0 && split < n, "sp_conv2d_wgrad_accum_pair: bad args");
+    const WgArgs a = {dtype, n, split, h, w_, cin_p, cout, ld_dy, ksize, dy_pooled, {dbias_a != nullptr, dbias_b != nullptr}, false,
+                      workspace ? workspace_floats : 0};
+    const WgPtrs p = {x, dy, dw_a, dbias_a, dw_b, dbias_b, nullptr, nullptr, workspace};
+    if (const int rc = wgrad_check("sp_conv2d_wgrad_accum_pair", a, &p)) return rc;
+    return wgrad_run(a, p, stream);
+}
+
+// The most scratch an accumulating entry point wants lent for these dimensions.  The query knows neither the split nor whether dy is
+// pooled, so it asks every family that could take the layer: the streaming and per-tap plans with all the scratch they may want, the
+// row walker by map.  (A group of a pair has fewer images; ops.py sizes the scratch for all n, and a per-tap plan that finds too little
+// drops to one split per tile.)
 extern "C" int sp_conv2d_wgrad_workspace(int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout, int32_t ksize,
                                          int32_t dtype, int64_t* floats_out) {
     SP_CHECK_ARG(floats_out && n > 0 && h > 0 && w_ > 0 && cin_p > 0 && cout > 0 && (ksize == 1 || ksize == 3), "sp_conv2d_wgrad_workspace: bad args");
-    // scratch the row-walker kernel wants for its per-block partial tiles (bf16, 3x3, W % 32 == 0) ...
-    int64_t need = (dtype == SP_BF16 && ksize == 3 && sp_tune(SP_TUNE_WGRAD_ROWS, 1)) ? (int64_t)sp_wgrad_rows_workspace(n, h, w_, cin_p, cout) : 0;
-    if (dtype == SP_BF16 && ksize == 3 && cin_p == 8) {
-        const int64_t s8 = sp_wgrad3x3_cin8_workspace(n, h, w_, cout, (cout + 7) & ~7);
-        if (s8 > need) need = s8;
+    const long all = 1L << 62;
+    const int ld = (cout + 7) & ~7;
+    long need = 0;
+    if (dtype == SP_BF16 && ksize == 3) {
+        // the row walker's per-block partial tiles ...
+        if (sp_tune(SP_TUNE_WGRAD_ROWS, 1)) need = sp_wgrad_rows_workspace(h, w_);
+        if (cin_p == 8) need = std::max(need, sp_wgrad3x3_cin8_plan(n, 0, h, w_, cout, ld, all).ws_need);
     }
-    // ... the per-split slabs of the streaming 1x1 kernel ...
-    if (dtype == SP_BF16 && ksize == 1) {
-        const int64_t s1 = sp_wgrad1x1_workspace(n, h, w_, cin_p, cout, (cout + 7) & ~7);
-        if (s1 > need) need = s1;
-    }
+    // ... the per-split slabs of the streaming kernels ...
+    if (dtype == SP_BF16 && ksize == 1) need = sp_wgrad1x1_plan(n, 0, h, w_, cin_p, cout, ld, all).ws_need;
     // ... and, in the deterministic mode, the per-split slabs of the per-tap kernels for every other shape
-    if (sp_deterministic(dtype)) {
-        const int64_t slab = dtype == SP_F32 ? pertap_slab_floats<float>(n, h, w_, cin_p, cout, ksize) : pertap_slab_floats<bf16>(n, h, w_, cin_p, cout, ksize);
-        if (slab > need) need = slab;
-    }
+    if (sp_deterministic(dtype))
+        need = std::max(need, pertap_slab_floats(dtype == SP_F32 ? pertap_plan<float>(n, h, w_, cin_p, cout, ksize) : pertap_plan<bf16>(n, h, w_, cin_p, cout, ksize),
+                                                 cin_p, cout, ksize));
     *floats_out = need;
     return SP_OK;
 }
@@ -790,16 +912,12 @@ extern "C" int sp_conv2d_wgrad_fused(const void* x, const void* dy, float* dw, f
                                      float* dot, float* workspace, int64_t workspace_floats, int32_t n, int32_t h,
                                      int32_t w_, int32_t cin_p, int32_t cout, int32_t ld_dy, int32_t ksize,
                                      int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(x && dy && dw, "sp_conv2d_wgrad: null pointer");
-    SP_CHECK_ARG(ksize == 1 || ksize == 3, "sp_conv2d_wgrad: ksize %d unsupported", ksize);
-    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_conv2d_wgrad: bad dtype %d", dtype);
-    const int e = dtype == SP_F32 ? 4 : 8;
-    SP_CHECK_ARG(cin_p % e == 0 && ld_dy % e == 0, "sp_conv2d_wgrad: cin_p=%d and ld_dy=%d must be multiples of %d", cin_p, ld_dy, e);
-    SP_CHECK_ARG(n > 0 && h > 0 && w_ > 0 && cout > 0 && cout <= ld_dy, "sp_conv2d_wgrad: bad dims");
+    const WgArgs a = {dtype, n, 0, h, w_, cin_p, cout, ld_dy, ksize, 0, {dbias != nullptr, false}, w_packed != nullptr, workspace ? workspace_floats : 0};
+    const WgPtrs p = {x, dy, dw, dbias, nullptr, nullptr, w_packed, w_packed ? dot : nullptr, workspace};
+    if (const int rc = wgrad_check("sp_conv2d_wgrad", a, &p)) return rc;
     SP_CHECK_ARG(w_packed == nullptr || dot != nullptr, "sp_conv2d_wgrad: w_packed needs dot");
     // dot without w_packed: the slot is only zero-filled here (one fill for [dW | dot | dbias]) and sp_sn_backward
-    // (dot_ready = 3) accumulates into it.
-    if (!w_packed) { /* the kernels see dot == nullptr */ }
+    // (dot_ready = 3) accumulates into it; the kernels see dot == nullptr.
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t n_dw = (size_t)cout * ksize * ksize * cin_p;
     hipError_t err;
@@ -812,35 +930,25 @@ extern "C" int sp_conv2d_wgrad_fused(const void* x, const void* dy, float* dw, f
         if (err == hipSuccess && dot) err = hipMemsetAsync(dot, 0, sizeof(float), s);
     }
     if (err != hipSuccess) { sp_set_error("sp_conv2d_wgrad: memset failed: %s", hipGetErrorString(err)); return SP_ERR_LAUNCH; }
-    return dtype == SP_F32 ? dispatch_wgrad<float>(x, dy, dw, n, h, w_, cin_p, cout, ld_dy, ksize, dbias, w_packed, w_packed ? dot : nullptr, workspace, workspace_floats, s)
-                           : dispatch_wgrad<bf16>(x, dy, dw, n, h, w_, cin_p, cout, ld_dy, ksize, dbias, w_packed, w_packed ? dot : nullptr, workspace, workspace_floats, s);
+    return wgrad_run(a, p, stream);
 }
 
 extern "C" int sp_conv2d_wgrad_accum(const void* x, const void* dy, float* dw, float* dbias, float* workspace,
                                      int64_t workspace_floats, int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout,
                                      int32_t ld_dy, int32_t ksize, int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(x && dy && dw, "sp_conv2d_wgrad_accum: null pointer");
-    SP_CHECK_ARG(ksize == 1 || ksize == 3, "sp_conv2d_wgrad_accum: ksize %d unsupported", ksize);
-    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_conv2d_wgrad_accum: bad dtype %d", dtype);
-    const int e = dtype == SP_F32 ? 4 : 8;
-    SP_CHECK_ARG(cin_p % e == 0 && ld_dy % e == 0, "sp_conv2d_wgrad_accum: cin_p=%d and ld_dy=%d must be multiples of %d", cin_p, ld_dy, e);
-    SP_CHECK_ARG(n > 0 && h > 0 && w_ > 0 && cout > 0 && cout <= ld_dy, "sp_conv2d_wgrad_accum: bad dims");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return dtype == SP_F32 ? dispatch_wgrad<float>(x, dy, dw, n, h, w_, cin_p, cout, ld_dy, ksize, dbias, nullptr, nullptr, workspace, workspace_floats, s)
-                           : dispatch_wgrad<bf16>(x, dy, dw, n, h, w_, cin_p, cout, ld_dy, ksize, dbias, nullptr, nullptr, workspace, workspace_floats, s);
+    const WgArgs a = {dtype, n, 0, h, w_, cin_p, cout, ld_dy, ksize, 0, {dbias != nullptr, false}, false, workspace ? workspace_floats : 0};
+    const WgPtrs p = {x, dy, dw, dbias, nullptr, nullptr, nullptr, nullptr, workspace};
+    if (const int rc = wgrad_check("sp_conv2d_wgrad_accum", a, &p)) return rc;
+    return wgrad_run(a, p, stream);
 }
 
 extern "C" int sp_conv2d_wgrad_accum_pooled(const void* x, const void* dy, float* dw, float* dbias, float* workspace,
                                             int64_t workspace_floats, int32_t n, int32_t h, int32_t w_, int32_t cin_p, int32_t cout,
                                             int32_t ld_dy, int32_t ksize, int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(x && dy && dw, "sp_conv2d_wgrad_accum_pooled: null pointer");
-    SP_CHECK_ARG(ksize == 3 && dtype == SP_BF16, "sp_conv2d_wgrad_accum_pooled: bf16 3x3 layers only");
-    SP_CHECK_ARG(cin_p % 8 == 0 && ld_dy % 8 == 0, "sp_conv2d_wgrad_accum_pooled: cin_p=%d and ld_dy=%d must be multiples of 8", cin_p, ld_dy);
-    SP_CHECK_ARG(n > 0 && h > 0 && w_ > 0 && cout > 0 && cout <= ld_dy && h % 2 == 0 && w_ % 2 == 0, "sp_conv2d_wgrad_accum_pooled: bad dims");
-    const int rc = sp_wgrad_rows_launch(x, dy, dw, dbias, n, h, w_, cin_p, cout, ld_dy, workspace, workspace_floats, 1,
-                                        reinterpret_cast<hipStream_t>(stream));
-    SP_CHECK_ARG(rc != 1, "sp_conv2d_wgrad_accum_pooled: shape not covered by the row-walking kernel (w %% 32, h %% 2)");
-    return rc;
+    const WgArgs a = {dtype, n, 0, h, w_, cin_p, cout, ld_dy, ksize, 1, {dbias != nullptr, false}, false, workspace ? workspace_floats : 0};
+    const WgPtrs p = {x, dy, dw, dbias, nullptr, nullptr, nullptr, nullptr, workspace};
+    if (const int rc = wgrad_check("sp_conv2d_wgrad_accum_pooled", a, &p)) return rc;
+    return wgrad_run(a, p, stream);
 }
 
 extern "C" int sp_conv2d_wgrad(const void* x, const void* dy, float* dw, int32_t n, int32_t h, int32_t w_,

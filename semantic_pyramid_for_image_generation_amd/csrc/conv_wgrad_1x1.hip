@@ -367,11 +367,12 @@ __global__ __launch_bounds__(256) void wgrad1x1_reduce_kernel(const float* __res
     }
 }
 
-struct W1Plan { int tiles, ci_tiles, nsplit, stages_per_split; bool ok; };
-
 // the pixel split of a covered layer: ~target blocks (one per CU measured best: 128 / 192 / 256 / 384 / 512 -> 0.250 / 0.211 / 0.189 /
-// 0.201 / 0.197 ms over the step's fourteen shapes - more splits mean more slab traffic), at least four 64-pixel stages per split
-void w1_split(W1Plan& p, long M, int target) {
+// 0.201 / 0.197 ms over the step's fourteen shapes - more splits mean more slab traffic), at least four 64-pixel stages per split.
+// Split k covers the pixels [k, k + 1) * 64 * stages_per_split and leaves one slab: the plan is ok where the scratch lent holds the slabs
+// and, for the two groups of sp_conv2d_wgrad_accum_pair (their pixels meet at split_pixels), where that boundary falls between two
+// splits, so that every slab belongs to one group
+void w1_split(W1Plan& p, long M, int target, long split_pixels, long n_dw, int cout, long ws_floats) {
     const long stages = (M + 63) / 64;
     long nsplit = (target + p.tiles - 1) / p.tiles;
     if (nsplit > stages / 4) nsplit = stages / 4;
@@ -379,35 +380,11 @@ void w1_split(W1Plan& p, long M, int target) {
     const long sps = (stages + nsplit - 1) / nsplit;
     p.stages_per_split = (int)sps;
     p.nsplit = (int)((stages + sps - 1) / sps);
-    p.ok = true;
+    p.ws_need = p.nsplit <= 1 ? 0 : (long)p.nsplit * (n_dw + ((cout + 3) & ~3));
+    if (split_pixels > 0 && (p.nsplit <= 1 || split_pixels % (64 * sps) != 0)) return;
+    p.kb = (int)(split_pixels / (64 * sps));
+    p.ok = ws_floats >= p.ws_need;
 }
-
-W1Plan w1_plan(int n, int h, int w, int cin, int cout, int ld_dy) {
-    W1Plan p = {};
-    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
-    const long M = (long)n * h * w;
-    if (target <= 0 || cin % 8 != 0 || ld_dy % 8 != 0) return p;
-    if (M * cin * 2 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31)) return p;           // 32-bit buffer offsets
-    p.ci_tiles = (cin + 63) / 64;
-    p.tiles = p.ci_tiles * ((cout + 63) / 64);
-    w1_split(p, M, target);
-    return p;
-}
-
-// 3x3, 8-channel input (the padded RGB images): same contract, an im2col X tile of 72 columns
-W1Plan c8_plan(int n, int h, int w, int cout, int ld_dy) {
-    W1Plan p = {};
-    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
-    const long M = (long)n * h * w;
-    if (target <= 0 || (h & (h - 1)) != 0 || (w & (w - 1)) != 0 || ld_dy % 8 != 0) return p;
-    if (M * 16 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31) || M < 16384) return p;     // small maps: the row-walker is fine
-    p.ci_tiles = 1;
-    p.tiles = (cout + 63) / 64;
-    w1_split(p, M, target);
-    return p;
-}
-
-long w1_workspace(const W1Plan& p, long n_dw, int cout) { return (!p.ok || p.nsplit <= 1) ? 0 : (long)p.nsplit * (n_dw + ((cout + 3) & ~3)); }
 
 void w1_reduce(const W1Args& a, int k0, int k1, float* dw, float* dbias, hipStream_t s) {
     const float* bias_slabs = a.bias_slabs != nullptr ? a.bias_slabs + (long)k0 * a.bias_ld : nullptr;
@@ -417,16 +394,11 @@ void w1_reduce(const W1Args& a, int k0, int k1, float* dw, float* dbias, hipStre
                        bias_slabs, a.bias_ld, a.COUT, dbias);
 }
 
-// Plan -> W1Args -> slab admission -> launch -> reduce, for both streaming kernels (EXTRA: what KERNEL takes after its W1Args) and both
-// entry points: one group (dw_b == nullptr), or the two groups of sp_conv2d_wgrad_accum_pair, whose pixels meet at split_pixels.  Split k
-// covers the pixels [k, k + 1) * 64 * stages_per_split, so when the group boundary is a multiple of that every slab belongs to one
-// group and each group gets its own reduce pass.  SP_OK after launching, 1 if the layer is not covered (the caller falls back).
+// Plan -> W1Args -> launch -> reduce, for both streaming kernels (EXTRA: what KERNEL takes after its W1Args) and both forms: one group
+// (dw_b == nullptr), or two, each with its own reduce pass over its slabs
 template <auto KERNEL, int LDS, typename... EXTRA>
-int w1_launch_impl(const W1Plan& p, const char* route, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b,
-                   long split_pixels, long M, int cin, int taps, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s, EXTRA... extra) {
-    if (!p.ok) return 1;
-    const long px_per_split = 64L * p.stages_per_split;
-    if (dw_b != nullptr && (p.nsplit <= 1 || split_pixels % px_per_split != 0)) return 1;
+int w1_launch_impl(const W1Plan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long M, int cin, int taps,
+                   int cout, int ld_dy, float* ws, hipStream_t s, EXTRA... extra) {
     W1Args a;
     a.x = reinterpret_cast<const bf16*>(x);
     a.dy = reinterpret_cast<const bf16*>(dy);
@@ -440,21 +412,14 @@ int w1_launch_impl(const W1Plan& p, const char* route, const void* x, const void
     a.stages_per_split = p.stages_per_split;
     a.nsplit = p.nsplit;
     a.bias_ld = (cout + 3) & ~3;
-    a.slabs = nullptr;
-    a.bias_slabs = nullptr;
-    if (p.nsplit > 1) {
-        if (ws == nullptr || ws_floats < w1_workspace(p, a.n_dw, cout)) return 1;
-        a.slabs = ws;
-        a.bias_slabs = dbias != nullptr ? ws + (long)p.nsplit * a.n_dw : nullptr;
-    }
+    a.slabs = p.nsplit > 1 ? ws : nullptr;
+    a.bias_slabs = (p.nsplit > 1 && dbias != nullptr) ? ws + (long)p.nsplit * a.n_dw : nullptr;
     if (const int rc = sp_lds_limit<KERNEL>(LDS)) return rc;
-    sp_note_route(route);
     hipLaunchKernelGGL(KERNEL, dim3((unsigned)(p.tiles * (p.nsplit >= 8 ? ((p.nsplit + 7) / 8) * 8 : p.nsplit))), dim3(256), LDS, s, a, extra...);
     SP_LAUNCH_CHECK();
     if (dw_b != nullptr) {
-        const int kb = (int)(split_pixels / px_per_split);
-        w1_reduce(a, 0, kb, dw, dbias, s);
-        w1_reduce(a, kb, p.nsplit, dw_b, dbias_b, s);
+        w1_reduce(a, 0, p.kb, dw, dbias, s);
+        w1_reduce(a, p.kb, p.nsplit, dw_b, dbias_b, s);
     } else if (p.nsplit > 1) {
         w1_reduce(a, 0, p.nsplit, dw, dbias, s);
     }
@@ -462,43 +427,44 @@ int w1_launch_impl(const W1Plan& p, const char* route, const void* x, const void
     return SP_OK;
 }
 
-int c8_launch_impl(const char* route, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, long split_pixels, int n, int h,
-                   int w, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
+}  // namespace
+
+// split: 0 = one group, otherwise the first image of the second group; ws_floats: the scratch lent
+W1Plan sp_wgrad1x1_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, long ws_floats) {
+    W1Plan p = {};
+    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
+    const long M = (long)n * h * w;
+    if (target <= 0 || cin % 8 != 0 || ld_dy % 8 != 0) return p;
+    if (M * cin * 2 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31)) return p;           // 32-bit buffer offsets
+    p.ci_tiles = (cin + 63) / 64;
+    p.tiles = p.ci_tiles * ((cout + 63) / 64);
+    w1_split(p, M, target, (long)split * h * w, (long)cout * cin, cout, ws_floats);
+    return p;
+}
+
+int sp_wgrad1x1_launch(const W1Plan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int h, int w,
+                       int cin, int cout, int ld_dy, float* ws, hipStream_t s) {
+    return w1_launch_impl<wgrad1x1_stream_kernel, W1_LDS>(p, x, dy, dw, dbias, dw_b, dbias_b, (long)n * h * w, cin, 1, cout, ld_dy, ws, s);
+}
+
+// 3x3, 8-channel input (the padded RGB images): same contract, an im2col X tile of 72 columns
+W1Plan sp_wgrad3x3_cin8_plan(int n, int split, int h, int w, int cout, int ld_dy, long ws_floats) {
+    W1Plan p = {};
+    const int target = sp_tune(SP_TUNE_WGRAD1X1, 256);
+    const long M = (long)n * h * w;
+    if (target <= 0 || (h & (h - 1)) != 0 || (w & (w - 1)) != 0 || ld_dy % 8 != 0) return p;
+    if (M * 16 >= (1L << 31) || M * ld_dy * 2 >= (1L << 31) || M < 16384) return p;     // small maps: the row-walker is fine
+    p.ci_tiles = 1;
+    p.tiles = (cout + 63) / 64;
+    w1_split(p, M, target, (long)split * h * w, (long)cout * 72, cout, ws_floats);
+    return p;
+}
+
+int sp_wgrad3x3_cin8_launch(const W1Plan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int h, int w,
+                            int cout, int ld_dy, float* ws, hipStream_t s) {
     int logw = 0, logh = 0;
     while ((1 << logw) < w) ++logw;
     while ((1 << logh) < h) ++logh;
-    return w1_launch_impl<wgrad3x3_cin8_stream_kernel, C8_LDS>(c8_plan(n, h, w, cout, ld_dy), route, x, dy, dw, dbias, dw_b, dbias_b, split_pixels,
-                                                               (long)n * h * w, 8, 9, cout, ld_dy, ws, ws_floats, s, h, w, logw, logh);
-}
-
-}  // namespace
-
-long sp_wgrad1x1_workspace(int n, int h, int w, int cin, int cout, int ld_dy) { return w1_workspace(w1_plan(n, h, w, cin, cout, ld_dy), (long)cout * cin, cout); }
-
-int sp_wgrad1x1_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout, int ld_dy,
-                       float* ws, long ws_floats, hipStream_t s) {
-    return w1_launch_impl<wgrad1x1_stream_kernel, W1_LDS>(w1_plan(n, h, w, cin, cout, ld_dy), "wgrad1x1_stream + reduce", x, dy, dw, dbias, nullptr, nullptr, 0,
-                                                          (long)n * h * w, cin, 1, cout, ld_dy, ws, ws_floats, s);
-}
-
-// the two-group form: 1 unless the layer runs with slabs and the group boundary falls between two splits
-int sp_wgrad1x1_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h, int w,
-                            int cin, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
-    if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
-    return w1_launch_impl<wgrad1x1_stream_kernel, W1_LDS>(w1_plan(n, h, w, cin, cout, ld_dy), "wgrad1x1_stream (two groups) + 2 x reduce", x, dy, dw_a, dbias_a,
-                                                          dw_b, dbias_b, (long)split * h * w, (long)n * h * w, cin, 1, cout, ld_dy, ws, ws_floats, s);
-}
-
-long sp_wgrad3x3_cin8_workspace(int n, int h, int w, int cout, int ld_dy) { return w1_workspace(c8_plan(n, h, w, cout, ld_dy), (long)cout * 72, cout); }
-
-int sp_wgrad3x3_cin8_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cout, int ld_dy, float* ws,
-                            long ws_floats, hipStream_t s) {
-    return c8_launch_impl("wgrad3x3_cin8_stream + reduce", x, dy, dw, dbias, nullptr, nullptr, 0, n, h, w, cout, ld_dy, ws, ws_floats, s);
-}
-
-int sp_wgrad3x3_cin8_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split, int h,
-                                 int w, int cout, int ld_dy, float* ws, long ws_floats, hipStream_t s) {
-    if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
-    return c8_launch_impl("wgrad3x3_cin8_stream (two groups) + 2 x reduce", x, dy, dw_a, dbias_a, dw_b, dbias_b, (long)split * h * w, n, h, w, cout, ld_dy, ws,
-                          ws_floats, s);
+    return w1_launch_impl<wgrad3x3_cin8_stream_kernel, C8_LDS>(p, x, dy, dw, dbias, dw_b, dbias_b, (long)n * h * w, 8, 9, cout, ld_dy, ws, s, h, w, logw,
+                                                               logh);
 }

@@ -704,7 +704,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_reduce_kernel(const float
                                                                      int CIN, int COUT, int ci_tiles, const float* __restrict__ bias_part,
                                                                      float* __restrict__ dbias, int ordered, int kbeg, int kend) {
     // [kbeg, kend): the blocks (of every pair) whose partial tiles this launch adds - all of them, or the blocks that walked the rows
-    // of ONE group of a two-group batch (sp_wgrad_rows_launch_pair); nblk stays the number of slabs per pair (the slab stride)
+    // of ONE group of a two-group batch (sp_wgrad_rows_launch with dw_b); nblk stays the number of slabs per pair (the slab stride)
     const int co0 = (blockIdx.y / ci_tiles) * 64, ci0 = (blockIdx.y % ci_tiles) * 64;
     if (bias_part != nullptr && blockIdx.z == 0 && ci0 == 0 && (!ordered || blockIdx.x == 0)) {
         // bias gradient: the per-block partial sums of this co tile, split over the gridDim.x blocks of the pair and the four
@@ -748,34 +748,41 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_reduce_kernel(const float
 
 // narrow maps walk 2 (16 wide) or 4 (8 wide) images side by side.  16 x 16 maps gain (512 -> 512 at batch 20: 74.9 -> 49.7 us);
 // 8 x 8 maps have too few rows per block to amortise the pipeline ramp (24.0 -> 29.3 us) and stay on the per-tap kernel unless
-// SP_TUNE_WGRAD_ROWS = 3; 2 keeps every narrow map on the per-tap kernel
+// SP_TUNE_WGRAD_ROWS = 3; 2 keeps every narrow map on the per-tap kernel.  The maps the kernel walks at all: 0 = wide ones, 16 / 8 = narrow
+// ones, -1 = not covered
 int wr_narrow(int h, int w, int dy_up2) {
+    if (h % WR_R != 0) return -1;
     if (w % 32 == 0) return 0;
     const int mode = sp_tune(SP_TUNE_WGRAD_ROWS, 1);
     const bool covered = (w == 16 && mode != 2) || (w == 8 && mode == 3);
-    return (covered && h % WR_R == 0 && !dy_up2) ? w : -1;
+    return (covered && !dy_up2) ? w : -1;
 }
 
-enum WrForm { WR_ROWS_0, WR_ROWS_16, WR_ROWS_8, WR_PP3, WR_PP3_TIMING };
+// dW += the slabs [k0, k1) of every pair (all blocks, or the blocks that walked the rows of one group)
+void wr_reduce(const WrPlan& p, const WrArgs& a, int k0, int k1, float* dw, float* dbias, hipStream_t s) {
+    constexpr int TILE_BLOCKS = WR_TILE_FLOATS / 4 / 256;
+    int z = 512 / (TILE_BLOCKS * p.pairs);                 // ~512 reducer blocks
+    if (z > (k1 - k0) / 4) z = (k1 - k0) / 4;
+    if (z < 1 || p.ordered) z = 1;                         // deterministic mode: one ordered chain per element, no atomics
+    hipLaunchKernelGGL(conv_wgrad_rows_reduce_kernel, dim3(TILE_BLOCKS, (unsigned)p.pairs, (unsigned)z), dim3(256), 0, s, a.slabs, p.blocks, dw, a.CIN,
+                       a.COUT, a.ci_tiles, a.bias_part, dbias, p.ordered ? 1 : 0, k0, k1);
+}
 
-// What one launch does: filled by wr_plan from the dims, the scratch the caller lent and the tuning table (no HIP calls)
-struct WrPlan {
-    bool ok;                                 // false: not covered (the caller's other path takes the layer)
-    WrForm form;
-    int pairs, ci_tiles;                     // (co, ci) tile pairs = grid.y
-    int blocks;                              // blocks per pair = grid.x = slabs per pair
-    int rows_per_block, rows_total;          // ping-pong form: block b walks the flattened image rows [b, b + 1) * rows_per_block
-    int rows_per_unit, units, thin_mode;     // 4-wave form: block b takes the units b, b + blocks, ... (thin_mode: WrArgs)
-    bool slabs, bias_part;                   // partial tiles / bias rows go to the slab area + reduce pass (false: fp32 atomics)
-    bool ordered;                            // deterministic mode: one fixed-order chain per element in the reduce pass
-    int kb;                                  // two groups: the first block of the second group
-};
+template <auto KERNEL, typename... EXTRA>
+int wr_launch_kernel(const WrPlan& p, int threads, int lds, hipStream_t s, const WrArgs& a, EXTRA... extra) {
+    if (const int rc = sp_lds_limit<KERNEL>(lds)) return rc;
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)p.blocks, (unsigned)p.pairs), dim3(threads), lds, s, a, extra...);
+    return SP_OK;
+}
 
-// split: 0 = one group; otherwise the images [0, split) and [split, n) accumulate into different gradients (two groups)
-WrPlan wr_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, int dy_up2, bool have_dbias, long ws_floats) {
+}  // namespace
+
+// The plan of one launch, from the dims, the scratch the caller lent and the tuning table (no HIP calls).  Not ok: narrow or odd maps,
+// operands of 1 GiB, a deterministic or two-group launch without room for every block's slab, a group boundary inside a block.
+WrPlan sp_wgrad_rows_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, int dy_up2, bool have_dbias, long ws_floats) {
     WrPlan p = {};
     const int nw = wr_narrow(h, w, dy_up2);
-    if (nw < 0 || h % WR_R != 0) return p;
+    if (nw < 0) return p;
     if ((long)n * h * w * cin * 2 >= (1L << 30) || (long)n * h * w * ld_dy * 2 >= (1L << 30)) return p;
     // wide maps: the ping-pong form (one 8-wave block per CU, contiguous row ranges, half the partial tiles) unless SP_TUNE_WGRAD_PP = 0
     const int pp = nw == 0 ? sp_tune(SP_TUNE_WGRAD_PP, 1) : 0;
@@ -844,32 +851,15 @@ WrPlan wr_plan(int n, int split, int h, int w, int cin, int cout, int ld_dy, int
     return p;
 }
 
-// dW += the slabs [k0, k1) of every pair (all blocks, or the blocks that walked the rows of one group)
-void wr_reduce(const WrPlan& p, const WrArgs& a, int k0, int k1, float* dw, float* dbias, hipStream_t s) {
-    constexpr int TILE_BLOCKS = WR_TILE_FLOATS / 4 / 256;
-    int z = 512 / (TILE_BLOCKS * p.pairs);                 // ~512 reducer blocks
-    if (z > (k1 - k0) / 4) z = (k1 - k0) / 4;
-    if (z < 1 || p.ordered) z = 1;                         // deterministic mode: one ordered chain per element, no atomics
-    hipLaunchKernelGGL(conv_wgrad_rows_reduce_kernel, dim3(TILE_BLOCKS, (unsigned)p.pairs, (unsigned)z), dim3(256), 0, s, a.slabs, p.blocks, dw, a.CIN,
-                       a.COUT, a.ci_tiles, a.bias_part, dbias, p.ordered ? 1 : 0, k0, k1);
-}
+// partial tiles + partial bias sums of at most WR_MAX_SLABS blocks, for every map the plan walks - whatever the image count (the groups of a
+// pair plan on their own, with fewer images) and whether the slabs end up in use (the scratch lent also steers the block count)
+long sp_wgrad_rows_workspace(int h, int w) { return wr_narrow(h, w, 0) < 0 ? 0 : WR_WS_FLOATS; }
 
-template <auto KERNEL, typename... EXTRA>
-int wr_launch_kernel(const char* route, const WrPlan& p, int threads, int lds, hipStream_t s, const WrArgs& a, EXTRA... extra) {
-    if (const int rc = sp_lds_limit<KERNEL>(lds)) return rc;
-    sp_note_route(route);
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)p.blocks, (unsigned)p.pairs), dim3(threads), lds, s, a, extra...);
-    return SP_OK;
-}
-
-// Plan -> WrArgs -> launch -> reduce pass(es), for one group (dw_b == nullptr, split == 0) and for two: ONE launch of the ping-pong
-// form over all n images (a block walks a contiguous range of image rows, so when the group boundary falls between two blocks every
-// partial tile belongs to one group) and one reduce pass per group over that group's slabs.
-// SP_OK after launching, 1 if the shape / plan is not covered.
-int wr_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int split, int h, int w, int cin,
-                   int cout, int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
-    const WrPlan p = wr_plan(n, split, h, w, cin, cout, ld_dy, dy_up2, dbias != nullptr, ws != nullptr ? ws_floats : 0);
-    if (!p.ok) return 1;
+// Plan -> WrArgs -> launch -> reduce pass(es), for one group (dw_b == nullptr) and for two: ONE launch of the ping-pong form over all
+// n images (a block walks a contiguous range of image rows, so when the group boundary falls between two blocks every partial tile
+// belongs to one group) and one reduce pass per group over that group's slabs.
+int sp_wgrad_rows_launch(const WrPlan& p, const void* x, const void* dy, float* dw, float* dbias, float* dw_b, float* dbias_b, int n, int h, int w,
+                         int cin, int cout, int ld_dy, float* ws, int dy_up2, hipStream_t s) {
     WrArgs a;
     a.x = reinterpret_cast<const bf16*>(x);
     a.dy = reinterpret_cast<const bf16*>(dy);
@@ -883,15 +873,13 @@ int wr_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float
     a.ci_tiles = p.ci_tiles;
     a.thin_mode = p.thin_mode;
     a.dy_up2 = dy_up2;
-    const char* pp3_route = dw_b != nullptr ? "conv_wgrad_pp3 (row walker, ping-pong, two groups) + 2 x rows_reduce"
-                                            : "conv_wgrad_pp3 (row walker, ping-pong) + rows_reduce";
     int rc = SP_OK;
     switch (p.form) {
-        case WR_ROWS_0: rc = wr_launch_kernel<conv_wgrad_rows_kernel<0>>("conv_wgrad_rows<0> + rows_reduce", p, 256, WR_LDS, s, a); break;
-        case WR_ROWS_16: rc = wr_launch_kernel<conv_wgrad_rows_kernel<16>>("conv_wgrad_rows<16> + rows_reduce", p, 256, WR_LDS, s, a); break;
-        case WR_ROWS_8: rc = wr_launch_kernel<conv_wgrad_rows_kernel<8>>("conv_wgrad_rows<8> + rows_reduce", p, 256, WR_LDS, s, a); break;
-        case WR_PP3: rc = wr_launch_kernel<conv_wgrad_pp3_kernel<false>>(pp3_route, p, 512, WP3_LDS, s, a, p.rows_per_block, p.rows_total); break;
-        case WR_PP3_TIMING: rc = wr_launch_kernel<conv_wgrad_pp3_kernel<true>>(pp3_route, p, 512, WP3_LDS, s, a, p.rows_per_block, p.rows_total); break;
+        case WR_ROWS_0: rc = wr_launch_kernel<conv_wgrad_rows_kernel<0>>(p, 256, WR_LDS, s, a); break;
+        case WR_ROWS_16: rc = wr_launch_kernel<conv_wgrad_rows_kernel<16>>(p, 256, WR_LDS, s, a); break;
+        case WR_ROWS_8: rc = wr_launch_kernel<conv_wgrad_rows_kernel<8>>(p, 256, WR_LDS, s, a); break;
+        case WR_PP3: rc = wr_launch_kernel<conv_wgrad_pp3_kernel<false>>(p, 512, WP3_LDS, s, a, p.rows_per_block, p.rows_total); break;
+        case WR_PP3_TIMING: rc = wr_launch_kernel<conv_wgrad_pp3_kernel<true>>(p, 512, WP3_LDS, s, a, p.rows_per_block, p.rows_total); break;
     }
     if (rc != SP_OK) return rc;
     if (p.form == WR_PP3_TIMING) {
@@ -904,24 +892,4 @@ int wr_launch_impl(const void* x, const void* dy, float* dw, float* dbias, float
     }
     SP_LAUNCH_CHECK();
     return SP_OK;
-}
-
-}  // namespace
-
-// partial tiles + partial bias sums of at most WR_MAX_SLABS blocks, for every shape a form covers
-long sp_wgrad_rows_workspace(int n, int h, int w, int cin, int cout) {
-    return (wr_narrow(h, w, 0) < 0 || h % WR_R != 0) ? 0 : WR_WS_FLOATS;
-}
-
-int sp_wgrad_rows_launch(const void* x, const void* dy, float* dw, float* dbias, int n, int h, int w, int cin, int cout,
-                         int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
-    return wr_launch_impl(x, dy, dw, dbias, nullptr, nullptr, n, 0, h, w, cin, cout, ld_dy, ws, ws_floats, dy_up2, s);
-}
-
-// Two-group batch (sp_conv2d_wgrad_accum_pair): images [0, split) accumulate into (dw_a, dbias_a), the rest into (dw_b, dbias_b);
-// 1 where that takes two launches (the caller then runs the two groups separately)
-int sp_wgrad_rows_launch_pair(const void* x, const void* dy, float* dw_a, float* dbias_a, float* dw_b, float* dbias_b, int n, int split,
-                              int h, int w, int cin, int cout, int ld_dy, float* ws, long ws_floats, int dy_up2, hipStream_t s) {
-    if (split <= 0 || split >= n || (dbias_a == nullptr) != (dbias_b == nullptr)) return 1;
-    return wr_launch_impl(x, dy, dw_a, dbias_a, dw_b, dbias_b, n, split, h, w, cin, cout, ld_dy, ws, ws_floats, dy_up2, s);
 }

@@ -749,6 +749,7 @@ def set_tuning(key: int, value: int) -> None:
     L.call("sp_set_tuning", key, value)
     _CONV_WS_CACHE.clear()
     _WS_CACHE.clear()
+    _POOLED_WGRAD_CACHE.clear()
     _LIN_WS_CACHE.clear()
 
 
@@ -836,6 +837,7 @@ def act_backward(dy: torch.Tensor, y: torch.Tensor, act: int, c_pad: Optional[in
 
 
 _WS_CACHE = {}
+_POOLED_WGRAD_CACHE = {}
 _CONV_WS_CACHE = {}
 _LIN_WS_CACHE = {}
 
@@ -857,6 +859,22 @@ def wgrad_workspace_floats(n, h, w, cin_p, cout, ksize, dtype) -> int:
         out = ctypes.c_int64(0)
         L.call("sp_conv2d_wgrad_workspace", n, h, w, cin_p, cout, ksize, sp_dtype(dtype), ctypes.byref(out))
         v = _WS_CACHE[key] = int(out.value)
+    return v
+
+
+def wgrad_reads_pooled(n, split, h, w, cin_p, cout, ld_dy, ksize, want_dbias: bool, ws_floats, dtype) -> bool:
+    """Whether the weight gradient of a pool2 layer can read the gradient at the pooled resolution (sp_conv2d_wgrad_accum_pooled, or
+    sp_conv2d_wgrad_accum_pair with dy_pooled, for split > 0): the library's route query with the very arguments of the launch, cached per
+    shape.  False: the pooling's backward is written out first."""
+    key = (n, split, h, w, cin_p, cout, ld_dy, ksize, want_dbias, ws_floats, dtype)
+    v = _POOLED_WGRAD_CACHE.get(key)
+    if v is None:
+        try:
+            L.wgrad_route(n, split, h, w, cin_p, cout, ld_dy, ksize, 1, want_dbias, ws_floats, sp_dtype(dtype))
+            v = True
+        except L.SempyrError:
+            v = False
+        _POOLED_WGRAD_CACHE[key] = v
     return v
 
 
@@ -929,6 +947,22 @@ def _wgrad_aside(h: int, w: int) -> bool:
     weight-gradient and input-gradient launches each leave most CUs idle)."""
     lim = CFG.wgrad_side_stream
     return bool(lim) and (lim == 1 or h * w <= lim)
+
+
+def _wgrad_launch(entry: str, pointers, ws_floats: int, ints, operands, flops: float, shape, aside: bool = False, defer_ok: bool = True) -> None:
+    """One weight-gradient launch of `entry` (pointers, scratch, scratch floats, ints, stream): lends the scratch the library asked for,
+    then runs it under bench.py's probe (flops, shape), on the side stream (aside; operands: the tensors it reads there) or with its slab
+    reductions deferred (defer_ok: _launch_wgrad_deferring)."""
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=operands[0].device) if ws_floats else None
+
+    def launch():
+        L.call(entry, *pointers, ptr(ws), ws_floats, *ints, stream())
+    if KERNEL_PROBE is not None:
+        _probed("wgrad", flops, launch, shape)
+    elif aside:
+        _on_wgrad_stream(launch, [*operands, ws])
+    else:
+        _launch_wgrad_deferring(launch, ws, defer_ok)
 
 
 def join_wgrad_stream(device) -> None:
@@ -1014,12 +1048,13 @@ class _ConvFn(torch.autograd.Function):
             dz = dy
         dres = dz if cout_p == cout else None
         need = ctx.needs_input_grad
-        ws_floats = wgrad_workspace_floats(ctx.pair.split if ctx.pair is not None else n, h, w, cin_p, cout, ksize, dt) if need[1] else 0
+        ws_floats = wgrad_workspace_floats(n, h, w, cin_p, cout, ksize, dt) if need[1] else 0
         # gradient of the fused average pooling: every pooled gradient spreads (x 1/4) over its 2x2 window.  The input- and
         # weight-gradient kernels read the pooled tensor through that expansion (in_up2 / sp_conv2d_wgrad_accum_pooled) where
         # they can; otherwise it is written out first.
         up2 = ctx.pool2 and _POOL2_BWD_FUSED and is_16bit(dt) and (not need[0] or conv_pool2_ok(h, w, pl.cin, ksize)) \
-            and (not need[1] or ws_floats > 0)
+            and (not need[1] or wgrad_reads_pooled(n, ctx.pair.split if ctx.pair is not None else 0, h, w, cin_p, cout, cout_p, ksize, bool(need[2]),
+                                                   ws_floats, dt))
         if ctx.pool2 and not up2:
             dz_full = nhwc_empty(n, cout_p, h, w, dt, x.device)
             L.call("sp_avgpool2_bwd", ptr(dz), ptr(dz_full), n, h, w, cout_p, sp_dtype(dt), stream())
@@ -1044,45 +1079,29 @@ class _ConvFn(torch.autograd.Function):
                 raise L.SempyrError("a two-group pass needs the bank's direct gradients (ModelWrapper sets them up)")
             pa, pb = pair.call_a.layers[pl.slot], pair.call_b.layers[pl.slot]
             dwa, dwb = pair.call_a.dw_slot(pa), pair.call_b.dw_slot(pb)
-            want_bias = bias_needed(need, 2)
-            dba = pair.call_a.db_slot(pa) if want_bias else None
-            dbb = pair.call_b.db_slot(pb) if want_bias else None
-            wsg = wgrad_workspace_floats(n, h, w, cin_p, cout, ksize, dt)
-            ws = torch.empty(wsg, dtype=torch.float32, device=x.device) if wsg else None
-
-            def launch_wgrad():
-                # ONE launch over both groups where the row walker takes the layer (half the partial-tile traffic), else the two
-                # groups one after the other - decided inside the library (include/sempyr.h: sp_conv2d_wgrad_accum_pair)
-                L.call("sp_conv2d_wgrad_accum_pair", ptr(x), ptr(dz), ptr(dwa), ptr(dba), ptr(dwb), ptr(dbb), ptr(ws), wsg, n, pair.split, h, w,
-                       cin_p, cout, cout_p, ksize, 1 if up2 else 0, sp_dtype(dt), stream())
-            if KERNEL_PROBE is not None:
-                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, launch_wgrad, (ksize, cin_p, cout, h, w, n))
-            elif _wgrad_aside(h, w):
-                _on_wgrad_stream(launch_wgrad, [x, dz, ws])
-            else:
-                _launch_wgrad_deferring(launch_wgrad, ws)
+            dba = pair.call_a.db_slot(pa) if need[2] else None
+            dbb = pair.call_b.db_slot(pb) if need[2] else None
+            # ONE launch over both groups where the row walker takes the layer (half the partial-tile traffic), else the two
+            # groups one after the other - decided inside the library (include/sempyr.h: sp_conv2d_wgrad_accum_pair)
+            _wgrad_launch("sp_conv2d_wgrad_accum_pair", (ptr(x), ptr(dz), ptr(dwa), ptr(dba), ptr(dwb), ptr(dbb)), ws_floats,
+                          (n, pair.split, h, w, cin_p, cout, cout_p, ksize, 1 if up2 else 0, sp_dtype(dt)), (x, dz),
+                          2.0 * n * h * w * pl.cin * cout * ksize * ksize, (ksize, cin_p, cout, h, w, n), aside=_wgrad_aside(h, w))
             dh = dhb = _zero1(x.device)
         elif need[1]:
             # weight (+ bias) gradient accumulate into this layer's slots of the pass-wide arena; the spectral-norm
             # backward of all layers runs later, batched, in _SNBankFn.backward
             dwsn = pl.call.dw_slot(pl)
-            if bias_needed(need, 2):
+            if need[2]:
                 db = pl.call.db_slot(pl)
-            ws = torch.empty(ws_floats, dtype=torch.float32, device=x.device) if ws_floats else None
             direct_bias = db is not None and pl.call.bank.direct_grads
-            def launch_wgrad():
-                L.call("sp_conv2d_wgrad_accum_pooled" if up2 else "sp_conv2d_wgrad_accum", ptr(x), ptr(dz), ptr(dwsn), ptr(db), ptr(ws),
-                       ws_floats, n, h, w, cin_p, cout, cout_p, ksize, sp_dtype(dt), stream())
-            if KERNEL_PROBE is not None:
-                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, launch_wgrad, (ksize, cin_p, cout, h, w, n))
-            elif _wgrad_aside(h, w) and pl.call.bank.direct_grads:
-                _on_wgrad_stream(launch_wgrad, [x, dz, ws])
-            else:
-                _launch_wgrad_deferring(launch_wgrad, ws, defer_ok=db is None or pl.call.bank.direct_grads)
+            _wgrad_launch("sp_conv2d_wgrad_accum_pooled" if up2 else "sp_conv2d_wgrad_accum", (ptr(x), ptr(dz), ptr(dwsn), ptr(db)), ws_floats,
+                          (n, h, w, cin_p, cout, cout_p, ksize, sp_dtype(dt)), (x, dz), 2.0 * n * h * w * pl.cin * cout * ksize * ksize,
+                          (ksize, cin_p, cout, h, w, n), aside=_wgrad_aside(h, w) and pl.call.bank.direct_grads,
+                          defer_ok=db is None or pl.call.bank.direct_grads)
             dh = _zero1(x.device)
             if direct_bias:
                 db = None                # accumulated in the bank's persistent slot; _SNBankFn.backward assigns bias.grad
-        elif bias_needed(need, 2):
+        elif need[2]:
             db = torch.empty(cout, dtype=torch.float32, device=x.device)
             pooled = 4 if up2 else 1      # the bias gradient is the plain sum of the pooled gradient (4 x 1/4)
             part = torch.empty(512 * cout, dtype=torch.float32, device=x.device)
@@ -1092,10 +1111,6 @@ class _ConvFn(torch.autograd.Function):
                 raise L.SempyrError("residual gradient with padded channels is not supported")
         return (dx, dh, db, dres if ctx.has_res[0] and need[3] else None, dres if ctx.has_res[1] and need[4] else None,
                 None, None, None, None, None, None, None, dhb, None, None)
-
-
-def bias_needed(need, idx) -> bool:
-    return bool(need[idx])
 
 
 def sn_conv2d(x, module, ksize: int, act: int = ACT_NONE, res1=None, res2=None, premasked: bool = False, mask_input: bool = False,
@@ -1212,16 +1227,9 @@ class _ReusedLayerFn(torch.autograd.Function):
             cout_p = pad_channels(cout, dt)
             if cout_p != cout:
                 raise L.SempyrError("a reused layer needs an unpadded channel count")
-            ws_floats = wgrad_workspace_floats(n, h, w, cin_p, cout, ksize, dt)
-            ws = torch.empty(ws_floats, dtype=torch.float32, device=x.device) if ws_floats else None
-
-            def launch():
-                L.call("sp_conv2d_wgrad_accum", ptr(x), ptr(dy), ptr(dwsn), ptr(db), ptr(ws), ws_floats, n, h, w, cin_p, cout, cout_p, ksize,
-                       sp_dtype(dt), stream())
-            if KERNEL_PROBE is not None:
-                _probed("wgrad", 2.0 * n * h * w * pl.cin * cout * ksize * ksize, launch, (ksize, cin_p, cout, h, w, n))
-            else:
-                _launch_wgrad_deferring(launch, ws, defer_ok=db is None or pl.call.bank.direct_grads)
+            _wgrad_launch("sp_conv2d_wgrad_accum", (ptr(x), ptr(dy), ptr(dwsn), ptr(db)), wgrad_workspace_floats(n, h, w, cin_p, cout, ksize, dt),
+                          (n, h, w, cin_p, cout, cout_p, ksize, sp_dtype(dt)), (x, dy), 2.0 * n * h * w * pl.cin * cout * ksize * ksize,
+                          (ksize, cin_p, cout, h, w, n), defer_ok=db is None or pl.call.bank.direct_grads)
         else:
             dy = as_rows(dy, dt)
             b, k = x.shape

@@ -5,6 +5,8 @@ Tolerances: fp32 mode (exact-fp32 MFMA) 2e-4 of the tensor's max magnitude unles
 (bf16 storage + bf16 MFMA, fp32 accumulate) 3e-2.  Index / mask semantics (max-pool routing, feature
 masking, concat) are checked bit-exactly on fp32.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -535,6 +537,99 @@ def test_conv_route_query_names_the_kernel_that_runs(monkeypatch):
         ref = F.conv2d(x.float(), w.float().permute(0, 3, 1, 2), None, padding=k // 2)
         close(y, ref.cpu(), 8e-3 if dt == torch.bfloat16 else TOL[dt], want)
     assert len(planned) == len(ROUTE_CASES)
+
+
+WGRAD_ROUTE_CASES = [  # (route, dtype, n, split, h, w, cin, cout, ksize, pooled, bias gradient, knobs) - the smallest shape that reaches each name
+    ("wgrad3x3_cin8_stream + reduce", torch.bfloat16, 1, 0, 128, 128, 8, 16, 3, 0, 1, {}),
+    ("wgrad3x3_cin8_stream (two groups) + 2 x reduce", torch.bfloat16, 6, 3, 128, 128, 8, 16, 3, 0, 1, {}),
+    ("conv_wgrad_pp3 (row walker, ping-pong) + rows_reduce", torch.bfloat16, 1, 0, 8, 32, 16, 16, 3, 0, 1, {}),
+    ("conv_wgrad_pp3 (row walker, ping-pong) + rows_reduce", torch.bfloat16, 1, 0, 8, 32, 16, 16, 3, 1, 1, {}),
+    ("conv_wgrad_pp3 (row walker, ping-pong, two groups) + 2 x rows_reduce", torch.bfloat16, 2, 1, 8, 32, 16, 16, 3, 0, 1, {}),
+    ("conv_wgrad_rows<16> + rows_reduce", torch.bfloat16, 1, 0, 16, 16, 16, 16, 3, 0, 1, {}),
+    ("conv_wgrad_rows<8> + rows_reduce", torch.bfloat16, 1, 0, 8, 8, 16, 16, 3, 0, 1, {"SP_WGRAD_ROWS": 3}),
+    ("conv_wgrad_rows<0> + rows_reduce", torch.bfloat16, 1, 0, 8, 32, 16, 16, 3, 0, 1, {"SP_WGRAD_PP": 0}),
+    ("conv_wgrad9 (per-tap, <= 64 channels)", torch.float32, 1, 0, 8, 32, 16, 64, 3, 0, 1, {}),
+    ("conv_wgrad<f32> (per-tap)", torch.float32, 1, 0, 8, 32, 16, 65, 3, 0, 1, {}),
+    ("conv_wgrad<16bit> (per-tap)", torch.bfloat16, 1, 0, 8, 8, 16, 16, 3, 0, 0, {}),
+    ("wgrad1x1_stream + reduce", torch.bfloat16, 1, 0, 8, 8, 16, 16, 1, 0, 1, {}),
+    ("wgrad1x1_stream (two groups) + 2 x reduce", torch.bfloat16, 4, 2, 8, 16, 16, 16, 1, 0, 1, {}),
+]
+
+
+def test_wgrad_route_query_names_the_kernel_that_runs():
+    """sp_conv2d_wgrad_route, asked with the very arguments of an accumulating call, names the kernel sp_last_route reports after it - one
+    launch per route name, and one with the gradient at the pooled resolution - and that kernel computes the weight (and bias) gradient:
+    torch's fp32 weight gradient on the same operands, per group; a pooled gradient stands for 1/4 x its nearest-neighbour expansion."""
+    g = torch.Generator(device="cuda").manual_seed(11)
+    for want, dt, n, split, h, w_, cin, cout, k, pooled, bias, knobs in WGRAD_ROUTE_CASES:
+        pad = 4 if dt == torch.float32 else 8
+        cp = (cout + pad - 1) // pad * pad
+        x = ops.nhwc_empty(n, cin, h, w_, dt, "cuda").normal_(generator=g)
+        dy = ops.nhwc_empty(n, cp, h // 2 if pooled else h, w_ // 2 if pooled else w_, dt, "cuda").normal_(generator=g)
+        ndw = cout * k * k * cin
+        bufs = [torch.zeros(ndw + cout + 8, device="cuda") for _ in range(2 if split else 1)]
+        dws = [ops.ptr(b) for b in bufs]
+        dbs = [ctypes.c_void_p(b.data_ptr() + 4 * (ndw + 4)) if bias else None for b in bufs]
+        for key, v in knobs.items():
+            ops.set_tuning(L.TUNE_KEYS[key], v)
+        try:
+            floats = ops.wgrad_workspace_floats(n, h, w_, cin, cout, k, dt)
+            ws = torch.empty(floats, device="cuda") if floats else None
+            asked = L.wgrad_route(n, split, h, w_, cin, cout, cp, k, pooled, bias, floats, ops.sp_dtype(dt))
+            if split:
+                L.call("sp_conv2d_wgrad_accum_pair", ops.ptr(x), ops.ptr(dy), dws[0], dbs[0], dws[1], dbs[1], ops.ptr(ws), floats, n, split, h, w_, cin,
+                       cout, cp, k, pooled, ops.sp_dtype(dt), ops.stream())
+            else:
+                L.call("sp_conv2d_wgrad_accum_pooled" if pooled else "sp_conv2d_wgrad_accum", ops.ptr(x), ops.ptr(dy), dws[0], dbs[0], ops.ptr(ws), floats,
+                       n, h, w_, cin, cout, cp, k, ops.sp_dtype(dt), ops.stream())
+        finally:
+            for key in knobs:
+                ops.set_tuning(L.TUNE_KEYS[key], -1)
+        assert asked == L.lib().sp_last_route().decode() == want, (want, asked, L.lib().sp_last_route().decode())
+        dyf = dy.float()[:, :cout]
+        if pooled:
+            dyf = 0.25 * F.interpolate(dyf, scale_factor=2, mode="nearest")
+        for buf, lo, hi in zip(bufs, (0, split), (split or n, n)):
+            wref = torch.zeros(cout, cin, k, k, device="cuda", requires_grad=True)
+            F.conv2d(x.float()[lo:hi], wref, padding=k // 2).backward(dyf[lo:hi])
+            close(buf[:ndw].view(cout, k * k, cin), wref.grad.permute(0, 2, 3, 1).reshape(cout, k * k, cin).cpu(), TOL[dt], "dW " + want)
+            if bias:
+                close(buf[ndw + 4:ndw + 4 + cout], dyf[lo:hi].sum((0, 2, 3)).cpu(), TOL[dt], "dbias " + want)
+
+
+def test_pooled_layer_the_row_walker_declines_takes_the_written_out_path(monkeypatch):
+    """A pool2 layer whose weight gradient the row walker declines - deterministic mode, 24 x 24 = 576 tile pairs against the 512 slabs of its
+    scratch - writes the pooling's backward out (sp_avgpool2_bwd) and runs sp_conv2d_wgrad_accum on it instead of raising: the gradients
+    equal, bit for bit in this mode, those of the same layer with the fused backward switched off."""
+    dt = torch.bfloat16
+    ops.set_compute_dtype(dt)
+    m = models.SNConv2d(1536, 1536, 3).cuda()
+    xd = dev(rnd(1, 1536, 8, 32, seed=1), dt)
+    gy = dev(rnd(1, 1536, 4, 16, seed=2), dt)
+    called = []
+    call = L.call
+
+    def spy(name, *args):
+        called.append(name)
+        return call(name, *args)
+    monkeypatch.setattr(L, "call", spy)
+    ops.set_tuning(ops.TUNE_DETERMINISTIC, 1)
+    try:
+        grads = []
+        for fused in (True, False):
+            monkeypatch.setattr(ops, "_POOL2_BWD_FUSED", fused)
+            synth(m, 13, "c.")                      # same weights, u and v for both runs
+            m.zero_grad(set_to_none=True)
+            del called[:]
+            x = xd.clone().requires_grad_(True)
+            m(x, ops.ACT_NONE, None, None, pool2=True).backward(gy)
+            assert "sp_avgpool2_bwd" in called and "sp_conv2d_wgrad_accum" in called and "sp_conv2d_wgrad_accum_pooled" not in called
+            grads.append((m.weight_orig.grad.clone(), m.bias.grad.clone(), x.grad.clone()))
+    finally:
+        ops.set_tuning(ops.TUNE_DETERMINISTIC, -1)
+    assert float(grads[0][0].abs().max()) > 0
+    for a_, b_ in zip(*grads):
+        assert torch.equal(a_, b_)
 
 
 @pytest.mark.parametrize("case", [(20, 128, 512, 1, 0, False, True), (16, 520, 512, 0, 2, False, True), (32, 72, 256, 2, 0, True, False),
