@@ -601,6 +601,30 @@ int sp_adam_multi_guarded(const sp_adam_chunk* chunks_dev, int32_t n_chunks, dou
 int sp_loss_scale_update(float* state, float growth, float backoff, int32_t interval, sp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exponential moving average (EMA) of a network's parameters, kept on the device.  The reference has NO average of its own:
+ * it scores, samples and saves the raw last-iterate generator (validate() / inference() at model_wrapper.py:231-296, the checkpoint at
+ * model_wrapper.py:215-223).  These two entry points stand beside its generator step (optimizer .step() at model_wrapper.py:190):
+ *   sp_ema_multi   avg[i] = avg[i] + (p[i] - avg[i]) * one_minus_decay for every chunk in one launch, in fp32 and in Tensor.lerp_'s
+ *                  order (the form sp_adam_multi's first moment uses); launched right behind the optimizer step.  one_minus_decay
+ *                  must lie in [0, 1] (NaN is rejected).  skip_if_nonzero: NULL, or a device float - the launch changes NOTHING when it
+ *                  is non-zero (sp_adam_multi_guarded's meaning: the optimizer step it follows was skipped).
+ *   sp_swap_multi  exchanges avg[i] and p[i]: the average is evaluated (and saved) through the network's own parameter storage - no
+ *                  address changes, so captured graphs, the optimizer's chunk tables and the flat gradient buffer stay valid - and a
+ *                  second call puts the raw parameters back bit for bit.
+ * fp32 only; one 256-thread block per chunk (<= 65536 elements, as sp_adam_chunk), float4 where both pointers of a chunk are 16-byte
+ * aligned, scalar otherwise.  A chunk's two ranges must not overlap each other or another chunk's.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sp_ema_chunk {
+    float* avg;            /* the average's window (updated / exchanged in place) */
+    float* p;              /* parameter (read by sp_ema_multi, exchanged by sp_swap_multi) */
+    int32_t n;             /* elements in this chunk */
+    int32_t reserved;
+} sp_ema_chunk;
+int sp_ema_multi(const sp_ema_chunk* chunks_dev, int32_t n_chunks, float one_minus_decay, const float* skip_if_nonzero,
+                 sp_stream_t stream);
+int sp_swap_multi(const sp_ema_chunk* chunks_dev, int32_t n_chunks, sp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * FID: the Inception-v3 feature extractor (torchvision's Inception3, eval mode, transform_input=False) that
  * /root/reference/frechet_inception_distance.py:11-42 hooks at Mixed_7c, forward only (inception.hip).
  *

@@ -33,6 +33,8 @@ results beyond floating-point summation order.  The kernel library itself reads 
     vgg_fp8               SP_VGG_FP8             0        BASELINE.json config 5's fp8 slice: VGG-16's wide 3x3 layers on the fp8 MFMA in the no-gradient pass (ops.set_vgg_fp8)
     inception_weights     SP_INCEPTION_WEIGHTS   ""       path of a torchvision inception_v3 state dict: ModelWrapper.validate() computes the FID with it
                                                           (inception.InceptionV3Features); empty = validate() returns nan
+    g_ema                 SP_G_EMA               0        decay of an exponential moving average of the generator's parameters (optim.ParameterEMA) that ModelWrapper
+                                                          keeps, evaluates (validate / inference) and saves; 0 = off: no launch, no allocation, no checkpoint key
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -73,6 +75,7 @@ class Config:
     bn_pair_upsample: bool = True
     defer_wgrad_reduce: bool = True
     inception_weights: str = ""
+    g_ema: float = 0.0
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -88,7 +91,7 @@ class Config:
                    fuse_tail_grad=_flag("SP_FUSE_TAIL_GRAD", True), vgg_fc_joint=_flag("SP_VGG_FC_JOINT", True),
                    sn_skip_pack=_flag("SP_SN_SKIP_PACK", True), bn_pair=_flag("SP_BN_PAIR", True),
                    bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True),
-                   inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""))
+                   inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0))
 
 
 CFG = Config.from_env()

@@ -8,6 +8,8 @@
 //   v   = v * beta2 + (1 - beta2) * g' * g'           (mul_ + addcmul_)
 //   p  -= step_size * m / (sqrt(v) / sqrt(bc2) + eps), step_size = lr / bc1  (per-tensor scalars: the step count is
 //                                                      per parameter, so they travel in the chunk table)
+// Beside it, in the same one-block-per-chunk form: the exponential moving average of a network's parameters and the in-place exchange
+// that evaluates it (sp_ema_multi / sp_swap_multi; the reference has no average).
 #include "common.h"
 
 namespace {
@@ -43,6 +45,39 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sp_adam_chunk* __
         c.p[i] = c.p[i] - c.step_size * (m / denom);
         c.m[i] = m;
         c.v[i] = v;
+    }
+}
+
+// Exponential moving average of a network's parameters (sp_ema_multi) and the in-place exchange that evaluates it (sp_swap_multi):
+// one block per chunk, the form of adam_multi_kernel.  avg += (p - avg) * (1 - decay) is Tensor.lerp_'s order, as for Adam's m.
+__global__ __launch_bounds__(256) void ema_multi_kernel(const sp_ema_chunk* __restrict__ chunks, float omd, const float* __restrict__ skip) {
+    if (skip != nullptr && *skip != 0.f) return;          // the optimizer step was skipped (non-finite gradients): the average stays too
+    const sp_ema_chunk c = chunks[blockIdx.x];
+    const bool vec = (((uintptr_t)c.avg | (uintptr_t)c.p) & 15) == 0;
+    const int n4 = vec ? c.n >> 2 : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        float4 a = reinterpret_cast<float4*>(c.avg)[i];
+        const float4 p = reinterpret_cast<const float4*>(c.p)[i];
+        a.x = a.x + (p.x - a.x) * omd; a.y = a.y + (p.y - a.y) * omd; a.z = a.z + (p.z - a.z) * omd; a.w = a.w + (p.w - a.w) * omd;
+        reinterpret_cast<float4*>(c.avg)[i] = a;
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < c.n; i += 256) c.avg[i] = c.avg[i] + (c.p[i] - c.avg[i]) * omd;
+}
+
+__global__ __launch_bounds__(256) void swap_multi_kernel(const sp_ema_chunk* __restrict__ chunks) {
+    const sp_ema_chunk c = chunks[blockIdx.x];
+    const bool vec = (((uintptr_t)c.avg | (uintptr_t)c.p) & 15) == 0;
+    const int n4 = vec ? c.n >> 2 : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const float4 a = reinterpret_cast<float4*>(c.avg)[i];
+        const float4 p = reinterpret_cast<float4*>(c.p)[i];
+        reinterpret_cast<float4*>(c.avg)[i] = p;
+        reinterpret_cast<float4*>(c.p)[i] = a;
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < c.n; i += 256) {
+        const float a = c.avg[i], p = c.p[i];
+        c.avg[i] = p;
+        c.p[i] = a;
     }
 }
 
@@ -141,4 +176,21 @@ extern "C" int sp_adam_multi_guarded(const sp_adam_chunk* chunks_dev, int32_t n_
 extern "C" int sp_adam_multi(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double beta1, double beta2, double eps,
                              double weight_decay, sp_stream_t stream) {
     return sp_adam_multi_guarded(chunks_dev, n_chunks, beta1, beta2, eps, weight_decay, nullptr, stream);
+}
+
+extern "C" int sp_ema_multi(const sp_ema_chunk* chunks_dev, int32_t n_chunks, float one_minus_decay, const float* skip_if_nonzero,
+                            sp_stream_t stream) {
+    SP_CHECK_ARG(chunks_dev && n_chunks > 0 && one_minus_decay >= 0.f && one_minus_decay <= 1.f,
+                 "sp_ema_multi: bad args (chunk table, n_chunks > 0, 0 <= one_minus_decay <= 1)");
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), chunks_dev, one_minus_decay,
+                       skip_if_nonzero);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_swap_multi(const sp_ema_chunk* chunks_dev, int32_t n_chunks, sp_stream_t stream) {
+    SP_CHECK_ARG(chunks_dev && n_chunks > 0, "sp_swap_multi: bad args (chunk table, n_chunks > 0)");
+    hipLaunchKernelGGL(swap_multi_kernel, dim3(n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), chunks_dev);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
 }

@@ -13,6 +13,9 @@ What differs from the reference, without changing any observable result (SURVEY.
 (inception.InceptionV3Features) when it has weights - the constructor's ``inception`` keyword or SP_INCEPTION_WEIGHTS, a
 torchvision inception_v3 state dict - and returns nan without them; ``inference`` writes the reference's 7 x 7 sample grid as a
 PNG (misc.save_image_grid - torchvision is not a dependency).
+Beyond the reference: with ``generator_ema`` (or SP_G_EMA) an exponential moving average of the generator's parameters is kept on the
+device (optim.ParameterEMA), updated behind every generator optimizer step, swapped in for ``validate`` / ``inference`` and saved
+beside the four reference keys of a checkpoint.  Off by default: nothing of it runs then.
 """
 from __future__ import annotations
 
@@ -48,7 +51,8 @@ class ModelWrapper(object):
                  diversity_loss: nn.Module = None,
                  save_data_path: Optional[str] = 'saved_data',
                  gradient_reducer=None,
-                 inception=None) -> None:
+                 inception=None,
+                 generator_ema=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -79,6 +83,19 @@ class ModelWrapper(object):
         for name in ('generator', 'discriminator', 'vgg16', 'generator_optimizer', 'discriminator_optimizer',
                      'generator_loss', 'discriminator_loss', 'diversity_loss', 'semantic_reconstruction_loss'):
             self.logger.hyperparameter[name] = str(getattr(self, name))
+        # generator_ema: a decay or an optim.ParameterEMA; None: CFG.g_ema (SP_G_EMA - the reference's main.py builds the wrapper with
+        # fixed keywords), 0 = off.  The average needs the generator on the GPU already (main.py:58 puts it there).
+        self.generator_ema = None
+        if generator_ema is None:
+            generator_ema = CFG.g_ema
+        if generator_ema:
+            from . import optim
+            if not isinstance(generator_ema, optim.ParameterEMA):
+                if isinstance(generator_ema, bool):
+                    raise ops.L.SempyrError("generator_ema takes a decay or an optim.ParameterEMA")
+                generator_ema = optim.ParameterEMA(self.generator, decay=float(generator_ema))
+            self.generator_ema = generator_ema
+            self.logger.hyperparameter['generator_ema'] = str({"decay": self.generator_ema.decay, "warmup": self.generator_ema.warmup})
         self._d_params = [p for p in self.discriminator.parameters()]
         self._g_params = [p for p in self.generator.parameters()]
         # every gradient of a network lives in ONE flat fp32 buffer (ops.SpectralNormBank.flat; param.grad are views of it):
@@ -172,18 +189,27 @@ class ModelWrapper(object):
         """optimizer.step() - in the fp16 storage mode behind the overflow guard of the dynamic loss scale (ops.LossScaler): the
         network's flat gradient buffer (already averaged over the ranks, so every rank decides alike) is screened for inf / NaN, the
         step is skipped where one is found, and the scale is backed off / grown - all on the device for this package's Adam
-        (sp_adam_multi_guarded); a foreign optimizer costs one host sync per step for the same decision."""
+        (sp_adam_multi_guarded); a foreign optimizer costs one host sync per step for the same decision.  The generator's step
+        (key "g") ends with the update of its weight average where there is one (self.generator_ema): one more eager launch, skipped
+        with the step - on the device through the same flag (read before sc.update() clears it), or on the host."""
+        ema = self.generator_ema if key == "g" else None
         bank = self._banks.get(key)
         sc = ops.loss_scaler(bank.flat.device) if bank is not None and bank.flat is not None else None
         if sc is None:
             optimizer.step()
+            if ema is not None:
+                ema.update()
             return
         from . import optim
         sc.check(bank.flat)
         if isinstance(optimizer, optim.Adam):
             optimizer.step(found_inf=sc.found_ptr)
+            if ema is not None:
+                ema.update(found_inf=sc.found_ptr)
         elif not sc.values()["found"]:
             optimizer.step()
+            if ema is not None:
+                ema.update()
         sc.update()
 
     # ------------------------------------------------------------------------------------------
@@ -678,19 +704,51 @@ class ModelWrapper(object):
                     if self.path_save_metrics is not None:
                         self.logger.save_metrics(self.path_save_metrics)
             if epoch % save_model_after_n_epochs == 0 and self.path_save_models is not None:
-                torch.save({"generator": self.generator.state_dict(),
-                            "discriminator": self.discriminator.state_dict(),
-                            "generator_optimizer": self.generator_optimizer.state_dict(),
-                            "discriminator_optimizer": self.discriminator_optimizer.state_dict()},
+                checkpoint = {"generator": self.generator.state_dict(),
+                              "discriminator": self.discriminator.state_dict(),
+                              "generator_optimizer": self.generator_optimizer.state_dict(),
+                              "discriminator_optimizer": self.discriminator_optimizer.state_dict()}
+                ema = self.generator_ema
+                if ema is not None and ema.num_updates > 0:
+                    # beyond the four reference keys: a state dict a Generator loads as it is (averaged parameters, live buffers)
+                    checkpoint["generator_ema"] = ema.averaged_state_dict(self.generator)
+                    checkpoint["generator_ema_state"] = {"decay": ema.decay, "warmup": ema.warmup, "num_updates": ema.num_updates}
+                torch.save(checkpoint,
                            os.path.join(self.path_save_models, 'checkpoint_{}.pt'.format(str(epoch).zfill(3))))
             self.inference(device=device)
             if self.path_save_metrics is not None:
                 self.logger.save_metrics(self.path_save_metrics)
         self.progress_bar.close()
 
+    def load_generator_ema(self, checkpoint_or_state) -> None:
+        """Restores the generator's weight average for a resumed run (the reference's main.py does not): a checkpoint of train()
+        (its "generator_ema" / "generator_ema_state" keys) or a ParameterEMA.state_dict()."""
+        ema = self.generator_ema
+        if ema is None:
+            raise ops.L.SempyrError("load_generator_ema(): this ModelWrapper keeps no generator average (generator_ema / SP_G_EMA)")
+        state = checkpoint_or_state
+        if "parameters" not in state:
+            if "generator_ema" not in state:
+                raise ops.L.SempyrError("load_generator_ema(): neither a ParameterEMA state nor a checkpoint with a 'generator_ema' key")
+            state = dict(state.get("generator_ema_state", {}), parameters=state["generator_ema"])
+        ema.load_state_dict(state)
+
+    def _ema_scope(self, use_ema):
+        """The context validate() / inference() run in: the generator's weight average swapped in (ParameterEMA.applied) where one
+        exists and use_ema is None or true, else nothing.  use_ema=True without an average is an error."""
+        import contextlib
+        ema = self.generator_ema
+        have = ema is not None and ema.num_updates > 0
+        if use_ema and not have:
+            raise ops.L.SempyrError("use_ema=True: there is no generator average (generator_ema / SP_G_EMA off, or no update yet)")
+        if have and (use_ema is None or use_ema):
+            return ema.applied()
+        return contextlib.nullcontext()
+
     @torch.no_grad()
-    def validate(self, device: str = 'cuda') -> float:
-        """model_wrapper.py:231-244: the FID over the validation loader, generator in eval mode and back in train mode afterwards.
+    def validate(self, device: str = 'cuda', use_ema=None) -> float:
+        """With a generator weight average (generator_ema) the FID is the AVERAGED generator's unless use_ema is False.
+        model_wrapper.py:231-244: the FID over the validation loader, generator in eval mode and back in train mode afterwards.
         The Inception-v3 weights are the constructor's ``inception`` or else CFG.inception_weights (SP_INCEPTION_WEIGHTS); with
         neither (or no validation loader) the result is nan.  `device` is accepted for main.py:111's call and ignored: the
         networks run where the generator's parameters are."""
@@ -703,18 +761,20 @@ class ModelWrapper(object):
             src = InceptionV3Features(src)
             self._inception = src                  # built once
         dev = next(self.generator.parameters()).device
-        self.generator.eval()
-        self.vgg16.eval()
-        try:
-            fid = frechet_inception_distance(dataset_real=self.validation_dataset_fid, generator=self.generator, vgg16=self.vgg16,
-                                             device=dev, inception=src)
-        finally:
-            self.generator.train()
+        with self._ema_scope(use_ema):
+            self.generator.eval()
+            self.vgg16.eval()
+            try:
+                fid = frechet_inception_distance(dataset_real=self.validation_dataset_fid, generator=self.generator, vgg16=self.vgg16,
+                                                 device=dev, inception=src)
+            finally:
+                self.generator.train()
         return float(fid)
 
     @torch.no_grad()
-    def inference(self, device: str = 'cuda') -> None:
-        """model_wrapper.py:247-296: 7 validation images x the 7 single-stage mask sets (misc.get_masks_for_inference), one fake image
+    def inference(self, device: str = 'cuda', use_ema=None) -> None:
+        """With a generator weight average (generator_ema) the samples are the AVERAGED generator's unless use_ema is False.
+        model_wrapper.py:247-296: 7 validation images x the 7 single-stage mask sets (misc.get_masks_for_inference), one fake image
         each from a fresh latent, generator in eval mode, saved as the reference's 7 x 7 grid ``predictions_<n>.png`` (every image
         scaled to [0, 1] by its own range, misc.normalize_0_1_batch); the generator goes back to training mode.  The draws follow the
         reference's order: np.random.choice over range(len(validation loader)), then one torch.randn per (image, stage)."""
@@ -724,22 +784,23 @@ class ModelWrapper(object):
         import numpy as np
         self.generator.to(device)
         self.vgg16.to(device)
-        self.generator.eval()
-        try:
-            idx = np.random.choice(range(len(self.validation_dataset_fid)), replace=False, size=7)
-            images, labels, _ = image_label_list_of_masks_collate_function([self.validation_dataset_fid.dataset[i] for i in idx])
-            masks_levels = [misc.get_masks_for_inference(stage, add_batch_size=True, device=device) for stage in range(7)]
-            fakes = torch.empty((7 ** 2,) + tuple(images.shape[1:]), dtype=torch.float32, device=device)
-            counter = 0
-            for image, label in zip(images, labels):
-                image, label = image.detach().to(device)[None], label.to(device)[None]
-                feats = self.vgg16(image)                      # (frozen, eval mode: the reference recomputes the same pyramid per stage)
-                for masks in masks_levels:
-                    z = torch.randn(1, self.latent_dimensions, dtype=torch.float32, device=device)
-                    fakes[counter] = self.generator(input=z, features=feats, masks=masks, class_id=label.float()).float()[0]
-                    counter += 1
-            n = getattr(self, "progress_bar", None)
-            misc.save_image_grid(misc.normalize_0_1_batch(fakes), os.path.join(self.path_save_plots, 'predictions_{}.png'.format(n.n if n is not None else 0)),
-                                 nrow=7)
-        finally:
-            self.generator.train()
+        with self._ema_scope(use_ema):
+            self.generator.eval()
+            try:
+                idx = np.random.choice(range(len(self.validation_dataset_fid)), replace=False, size=7)
+                images, labels, _ = image_label_list_of_masks_collate_function([self.validation_dataset_fid.dataset[i] for i in idx])
+                masks_levels = [misc.get_masks_for_inference(stage, add_batch_size=True, device=device) for stage in range(7)]
+                fakes = torch.empty((7 ** 2,) + tuple(images.shape[1:]), dtype=torch.float32, device=device)
+                counter = 0
+                for image, label in zip(images, labels):
+                    image, label = image.detach().to(device)[None], label.to(device)[None]
+                    feats = self.vgg16(image)                      # (frozen, eval mode: the reference recomputes the same pyramid per stage)
+                    for masks in masks_levels:
+                        z = torch.randn(1, self.latent_dimensions, dtype=torch.float32, device=device)
+                        fakes[counter] = self.generator(input=z, features=feats, masks=masks, class_id=label.float()).float()[0]
+                        counter += 1
+                n = getattr(self, "progress_bar", None)
+                misc.save_image_grid(misc.normalize_0_1_batch(fakes), os.path.join(self.path_save_plots, 'predictions_{}.png'.format(n.n if n is not None else 0)),
+                                     nrow=7)
+            finally:
+                self.generator.train()

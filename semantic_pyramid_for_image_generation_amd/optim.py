@@ -1,4 +1,5 @@
-"""Multi-tensor Adam on the HIP path.
+"""Multi-tensor Adam on the HIP path, and `ParameterEMA`: an exponential moving average of a network's parameters
+in one flat device buffer, updated by one launch behind the optimizer step and evaluated by exchanging it with the parameters in place.
 
 `Adam` IS a torch.optim.Adam (same constructor, param_groups, per-parameter state {step, exp_avg, exp_avg_sq} and
 state_dict, so checkpoints written by the reference - model_wrapper.py:215-223 - load unchanged); only `.step()` is
@@ -12,6 +13,8 @@ cached plan is dropped) - round 1 incremented 286 CPU tensors and rebuilt the ta
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -21,6 +24,7 @@ from .ops import ptr, stream
 CHUNK = 65536
 _DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i4"), ("step_size", "<f4"),
                 ("inv_sqrt_bc2", "<f4"), ("reserved", "<f4")])
+_EMA_DT = np.dtype([("avg", "<u8"), ("p", "<u8"), ("n", "<i4"), ("reserved", "<i4")])       # sp_ema_chunk (include/sempyr.h)
 
 
 class _Plan:
@@ -147,3 +151,174 @@ class Adam(torch.optim.Adam):
                 else:
                     L.call("sp_adam_multi", ptr(tab_dev), plan.total, float(b1), float(b2), eps, wd, stream())
         return loss
+
+
+class ParameterEMA:
+    """Exponential moving average of ``module``'s parameters on the device: avg += (p - avg) * (1 - decay) after every optimizer step.
+    The reference has no average of its own (it scores, samples and saves the last iterate: model_wrapper.py:231-296, :215-223); a
+    SAGAN-family generator trained at lr 1e-5 and batch 20 is normally evaluated from one.
+
+    There is no second network.  The average lives in ONE flat fp32 buffer (a window per parameter, in ``named_parameters()`` order,
+    each at an offset padded to 4 floats so that it is 16-byte aligned), and it is evaluated by exchanging its values with the
+    parameters' IN PLACE (`swap`, `applied`): no address changes, so captured graphs, Adam's cached chunk tables and the flat gradient
+    buffer stay valid, and the spectral-norm bank re-packs from ``weight_orig`` in every forward anyway.
+
+    What is averaged: the parameters, nothing else.  What is not: the buffers.  In eval mode a spectral-norm layer's sigma is
+    computed from the LIVE ``weight_u`` / ``weight_v`` against the averaged ``weight_orig`` (the power iteration tracks the raw
+    weights, a few 1e-5 steps away), and the BatchNorm running statistics (momentum 0.001) are slow averages already.
+
+    Host cost: the chunk table (pointers and lengths only - `sp_ema_chunk`) is built and uploaded once, and again only when a
+    parameter's ``data_ptr()`` or device changes; the buffer then follows the parameters to their device and keeps its values.
+    Parameters must be contiguous fp32 on one GPU (`SempyrError` otherwise): there is no fallback."""
+
+    def __init__(self, module, decay: float = 0.999, warmup: bool = False):
+        named = [(n, p) for n, p in module.named_parameters()]
+        if not named:
+            raise L.SempyrError("ParameterEMA: the module has no parameters")
+        self._params = [p for _, p in named]
+        self._check_params()
+        self._init_state([(n, tuple(p.shape)) for n, p in named], decay, warmup, self._params[0].device)
+
+    def _init_state(self, named_shapes, decay, warmup, device) -> None:
+        """Layout and storage (no kernel, no parameter is read): named_shapes = [(name, shape)] in named_parameters() order."""
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise L.SempyrError("ParameterEMA: decay must lie in [0, 1] (got %r)" % (decay,))
+        self.decay, self.warmup, self.num_updates = decay, bool(warmup), 0
+        self._names = [n for n, _ in named_shapes]
+        self._shapes = [tuple(s) for _, s in named_shapes]
+        self._numels = [int(np.prod(s, dtype=np.int64)) for s in self._shapes]
+        offs, off = [], 0
+        for n in self._numels:
+            offs.append(off)
+            off += (n + 3) // 4 * 4
+        self._offsets = offs
+        self.buffer = torch.zeros(max(off, 4), dtype=torch.float32, device=device)
+        self._windows = self._make_windows()
+        self._key, self._table_dev, self._total = None, None, 0
+        self._swapped = False
+
+    def _make_windows(self):
+        return [self.buffer[o:o + n].view(s) for o, n, s in zip(self._offsets, self._numels, self._shapes)]
+
+    def _check_params(self) -> None:
+        dev = self._params[0].device
+        for p in self._params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.device == dev):
+                raise L.SempyrError("ParameterEMA needs contiguous fp32 parameters on one GPU (got %s %s)" % (p.device, p.dtype))
+
+    def _plan(self):
+        """The device chunk table; rebuilt (and the buffer moved) only when a parameter's address or device has changed."""
+        key = tuple((p.data_ptr(), p.device) for p in self._params)
+        if key != self._key:
+            self._check_params()
+            dev = self._params[0].device
+            if self.buffer.device != dev:
+                self.buffer = self.buffer.to(dev)
+                self._windows = self._make_windows()
+            n = np.asarray(self._numels, dtype=np.int64)
+            reps = (n + CHUNK - 1) // CHUNK
+            total = int(reps.sum())
+            idx = np.repeat(np.arange(len(n)), reps)                           # tensor of each chunk
+            first = np.cumsum(reps) - reps
+            off = (np.arange(total) - first[idx]) * CHUNK                      # element offset of each chunk in its tensor
+            tab = np.zeros(total, dtype=_EMA_DT)
+            byte_off = (off * 4).astype(np.uint64)
+            tab["avg"] = np.uint64(self.buffer.data_ptr()) + (np.asarray(self._offsets, dtype=np.uint64) * np.uint64(4))[idx] + byte_off
+            tab["p"] = np.asarray([k[0] for k in key], dtype=np.uint64)[idx] + byte_off
+            tab["n"] = np.minimum(n[idx] - off, CHUNK).astype(np.int32)
+            self._total = total
+            self._table_dev = torch.from_numpy(tab.view(np.uint8).copy()).to(dev) if total else None      # static: uploaded once
+            self._key = key
+        return self._table_dev, self._total
+
+    # ------------------------------------------------------------------------------------------ update / swap
+    @torch.no_grad()
+    def update(self, found_inf=None) -> None:
+        """Call after the optimizer step.  The FIRST call only initialises the average to the parameters it sees (one
+        torch._foreach_copy_, no kernel); every later call is one sp_ema_multi launch on the current stream.  With ``warmup`` the
+        decay in force is min(decay, (1 + n) / (10 + n)), n = ``num_updates``: the calls made so far.  found_inf (optional, as in
+        `Adam.step`): a device float; the launch changes NOTHING when it is non-zero - the optimizer step it follows was skipped on
+        the device.  (The host-side counter ``num_updates`` still advances on such a skipped step, as Adam's step count does.)"""
+        if self._swapped:
+            raise L.SempyrError("ParameterEMA.update(): the average is swapped into the parameters - swap back first")
+        table, total = self._plan()
+        n = self.num_updates
+        self.num_updates = n + 1
+        if n == 0:
+            torch._foreach_copy_(self._windows, [p.detach() for p in self._params])
+            return
+        if total == 0:
+            return
+        decay = min(self.decay, (1.0 + n) / (10.0 + n)) if self.warmup else self.decay
+        with torch.cuda.device(self.buffer.device):
+            L.call("sp_ema_multi", ptr(table), total, 1.0 - decay, found_inf, stream())
+
+    def swap(self) -> None:
+        """Exchanges the average and the parameters in place (one sp_swap_multi launch on the current stream); a second call puts
+        both back bit for bit."""
+        if self.num_updates == 0:
+            raise L.SempyrError("ParameterEMA.swap(): the average has not been initialised (no update() yet, nothing loaded)")
+        table, total = self._plan()
+        if total:
+            with torch.cuda.device(self.buffer.device):
+                L.call("sp_swap_multi", ptr(table), total, stream())
+        self._swapped = not self._swapped
+
+    @property
+    def swapped(self) -> bool:
+        return self._swapped
+
+    @contextlib.contextmanager
+    def applied(self):
+        """``with ema.applied(): ...`` - the module holds the average inside the block and its own parameters after it (also when the
+        block raises).  Not re-entrant."""
+        if self._swapped:
+            raise L.SempyrError("ParameterEMA.applied(): already swapped in (nested use)")
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    # ------------------------------------------------------------------------------------------ state
+    def _average_tensors(self):
+        """Where the average is right now: its windows, or - while swapped in - the parameters."""
+        return [p.detach() for p in self._params] if self._swapped else self._windows
+
+    def state_dict(self):
+        return {"decay": self.decay, "warmup": self.warmup, "num_updates": self.num_updates,
+                "parameters": {n: t.clone() for n, t in zip(self._names, self._average_tensors())}}
+
+    @torch.no_grad()
+    def load_state_dict(self, state) -> None:
+        """``state``: what `state_dict` returns.  ``state["parameters"]`` may also be a plain state dict of the module (a generator's,
+        or `averaged_state_dict`'s): every parameter name must be there with its shape, buffers and other extra keys are ignored.
+        ``decay`` / ``warmup`` / ``num_updates`` are taken where present; a loaded average counts as initialised."""
+        if self._swapped:
+            raise L.SempyrError("ParameterEMA.load_state_dict(): the average is swapped into the parameters - swap back first")
+        tensors = state["parameters"]
+        missing = [n for n in self._names if n not in tensors]
+        if missing:
+            raise L.SempyrError("ParameterEMA.load_state_dict(): missing parameters %s" % (missing[:5],))
+        for n, s in zip(self._names, self._shapes):
+            if tuple(tensors[n].shape) != s:
+                raise L.SempyrError("ParameterEMA.load_state_dict(): %s has shape %s, expected %s" % (n, tuple(tensors[n].shape), s))
+        decay = float(state.get("decay", self.decay))
+        if not 0.0 <= decay <= 1.0:
+            raise L.SempyrError("ParameterEMA.load_state_dict(): decay must lie in [0, 1] (got %r)" % (decay,))
+        for n, w in zip(self._names, self._windows):
+            w.copy_(tensors[n])
+        self.decay, self.warmup = decay, bool(state.get("warmup", self.warmup))
+        self.num_updates = max(1, int(state.get("num_updates", self.num_updates)))
+
+    def averaged_state_dict(self, module):
+        """``module.state_dict()`` with every parameter replaced by (a copy of) its average; the buffers are the live ones (weight_u /
+        weight_v, BatchNorm running statistics, num_batches_tracked).  Loads straight into a Generator - this package's or the
+        reference's."""
+        out = module.state_dict()
+        for n, t in zip(self._names, self._average_tensors()):
+            if n not in out:
+                raise L.SempyrError("ParameterEMA.averaged_state_dict(): the module has no parameter %s" % n)
+            out[n] = t.clone()
+        return out
