@@ -451,6 +451,10 @@ int sp_attention_fwd(const void* q, const void* k, const void* v, void* o, float
 int sp_attention_bwd(const void* q, const void* k, const void* v, const void* dout, const float* lse, void* dq,
                      float* dk_f32, float* dv_f32, void* dk, void* dv_out, int32_t batch, int32_t n, int32_t nk,
                      int32_t d, int32_t dv, int32_t dtype, sp_stream_t stream);
+/* *fwd / *bwd = the kernel sp_attention_fwd / sp_attention_bwd would launch for these extents and this storage type: "mfma",
+ * "valu tq32" or "valu tq16" (the VALU kernels in their 32- and 16-query forms).  Same extent checks as the launchers, the same
+ * predicates as their dispatch; host-only like sp_conv2d_route: touches no device state, callable without a GPU. */
+int sp_attention_route(int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dtype, const char** fwd, const char** bwd);
 
 /* ------------------------------------------------------------------------------------------------
  * Glue: image ingest (NCHW/NHWC 3-channel source -> padded NHWC, optional affine = kornia.normalize at

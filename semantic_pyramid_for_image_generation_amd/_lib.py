@@ -152,6 +152,14 @@ def wgrad_route(n, split, h, w, cin_p, cout, ld_dy, ksize, dy_pooled, want_dbias
     return out.value.decode()
 
 
+def attention_route(n, nk, d, dv, dtype):
+    """(forward, backward) kernel names sp_attention_fwd / sp_attention_bwd would launch: "mfma", "valu tq32" or "valu tq16"
+    (include/sempyr.h: sp_attention_route; host-only)."""
+    fwd, bwd = ctypes.c_char_p(), ctypes.c_char_p()
+    call("sp_attention_route", n, nk, d, dv, dtype, ctypes.byref(fwd), ctypes.byref(bwd))
+    return fwd.value.decode(), bwd.value.decode()
+
+
 def call(name: str, *args) -> None:
     """Calls an int-returning entry point and raises SempyrError (with the library's message) on failure."""
     rc = getattr(lib(), name)(*args)

@@ -90,6 +90,12 @@ int main(void) {
     EXPECT(sp_conv2d_wgrad_accum_pair(&dummy, &dummy, (float*)&dummy, NULL, (float*)&dummy, NULL, NULL, 0, 2, 1, 8, 32, 12, 16, 16, 3, 0, SP_BF16, NULL) == SP_ERR_INVALID,
            "wgrad_accum_pair cin_p multiple");
     EXPECT(sp_conv2d_wgrad_accum_pooled(&dummy, &dummy, (float*)&dummy, NULL, NULL, 0, 2, 8, 24, 16, 16, 16, 3, SP_BF16, NULL) == SP_ERR_INVALID, "wgrad_accum_pooled w % 32");
+    const char* bwd = NULL;
+    EXPECT(sp_attention_route(70, 256, 64, 160, SP_BF16, &route, &bwd) == SP_OK && strcmp(route, "mfma") == 0 && strcmp(bwd, "mfma") == 0, "attention route mfma");
+    EXPECT(sp_attention_route(70, 256, 64, 240, SP_BF16, &route, &bwd) == SP_OK && strcmp(route, "mfma") == 0 && strcmp(bwd, "valu tq16") == 0, "attention route mixed");
+    EXPECT(sp_attention_route(70, 256, 64, 176, SP_F32, &route, &bwd) == SP_OK && strcmp(route, "valu tq32") == 0 && strcmp(bwd, "valu tq32") == 0, "attention route fp32");
+    EXPECT(sp_attention_route(70, 257, 64, 64, SP_BF16, &route, &bwd) == SP_ERR_INVALID, "attention route nk");
+    EXPECT(sp_attention_route(70, 256, 64, 64, SP_BF16, NULL, &bwd) == SP_ERR_INVALID, "attention route null");
     printf("asan_driver: %ld planner queries, %d failures\n", queries, fails);
     return fails != 0;
 }

@@ -9,7 +9,7 @@ cd "$(dirname "$0")"
 mkdir -p build/asan
 FLAGS="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result -fsanitize=address -fno-omit-frame-pointer"
 pids=()
-for f in conv_igemm conv_pp conv_ppw conv_wgrad conv_wgrad_rows conv_wgrad_1x1 reduce_queue; do
+for f in conv_igemm conv_pp conv_ppw conv_wgrad conv_wgrad_rows conv_wgrad_1x1 reduce_queue attention; do
   if [ ! -f build/asan/$f.o ] || [ $f.hip -nt build/asan/$f.o ] || [ common.h -nt build/asan/$f.o ] || [ conv_common.h -nt build/asan/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o build/asan/$f.o &
     pids+=($!)

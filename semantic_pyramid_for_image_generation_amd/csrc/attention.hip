@@ -565,9 +565,14 @@ inline int attn_valu_tq(int NK, int D, int DV) {
     const long lds_b32 = (long)(NK * (D + 1) + 32 * D + 32 * DV + 32 * NK + 32 * 4 + 32 * (NK + 1)) * 4;
     return lds_b32 <= 160 * 1024 ? 32 : 16;
 }
+// the two MFMA predicates: the launchers, sp_attention_bwd_slabs and sp_attention_route all ask these
+inline bool attn_fwd_mfma_ok(int dtype, int nk, int d, int dv) {
+    return dtype == SP_BF16 && d % 32 == 0 && dv % 16 == 0 && dv <= 256 && nk % 32 == 0;
+}
 inline bool attn_bwd_mfma_ok(int dtype, int nk, int d, int dv) {
     return dtype == SP_BF16 && (d == 32 || d == 64) && dv % 32 == 0 && dv <= 256 && nk % 32 == 0;
 }
+inline const char* attn_valu_name(int nk, int d, int dv) { return attn_valu_tq(nk, d, dv) == 32 ? "valu tq32" : "valu tq16"; }
 template <typename T>
 int launch_attn(bool fwd, const void* q, const void* k, const void* v, void* o_or_dq, const void* dout, float* lse, float* dk,
                 float* dv, int B, int N, int NK, int D, int DV, hipStream_t s) {
@@ -582,7 +587,7 @@ extern "C" int sp_attention_fwd(const void* q, const void* k, const void* v, voi
     SP_CHECK_ARG(q && k && v && o && lse, "sp_attention_fwd: null pointer");
     SP_CHECK_ARG(nk > 0 && nk <= 256 && d > 0 && d <= 64 && dv > 0 && dv <= 256, "sp_attention_fwd: unsupported extents nk=%d d=%d dv=%d", nk, d, dv);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == SP_BF16 && d % 32 == 0 && dv % 16 == 0 && dv <= 256 && nk % 32 == 0) {
+    if (attn_fwd_mfma_ok(dtype, nk, d, dv)) {
         const int lds = nk * (dv * 2 + 32);
         if (const int rc = sp_lds_limit<attn_fwd_mfma_kernel>(lds)) return rc;
         hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(sp_div_up(n, 64), batch), dim3(256), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
@@ -632,5 +637,14 @@ extern "C" int sp_attention_bwd(const void* q, const void* k, const void* v, con
 extern "C" int sp_attention_bwd_slabs(int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dtype, int64_t* slabs_out) {
     SP_CHECK_ARG(slabs_out && n > 0 && nk > 0 && d > 0 && dv > 0, "sp_attention_bwd_slabs: bad args");
     *slabs_out = attn_bwd_mfma_ok(dtype, nk, d, dv) ? sp_div_up(n, AB_QB) : sp_div_up(n, attn_valu_tq(nk, d, dv));
+    return SP_OK;
+}
+
+extern "C" int sp_attention_route(int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dtype, const char** fwd, const char** bwd) {
+    SP_CHECK_ARG(fwd != nullptr && bwd != nullptr, "sp_attention_route: null argument");
+    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_attention_route: unsupported storage type %d", dtype);
+    SP_CHECK_ARG(n > 0 && nk > 0 && nk <= 256 && d > 0 && d <= 64 && dv > 0 && dv <= 256, "sp_attention_route: unsupported extents n=%d nk=%d d=%d dv=%d", n, nk, d, dv);
+    *fwd = attn_fwd_mfma_ok(dtype, nk, d, dv) ? "mfma" : attn_valu_name(nk, d, dv);
+    *bwd = attn_bwd_mfma_ok(dtype, nk, d, dv) ? "mfma" : attn_valu_name(nk, d, dv);
     return SP_OK;
 }

@@ -7,8 +7,8 @@ its reason in the table).  Every case is launched twice into outputs pre-filled 
 persistent; where the pitch exceeds the channel count the sentinel beyond it must survive).
 
 Left out because they cannot be exact: tanh epilogues (every route the boundary table reaches through tanh is reached here through a
-pitch that is no multiple of 8, which takes the same general epilogue), the fp8 slice (its scales), attention, normalisation and
-resampling kernels."""
+pitch that is no multiple of 8, which takes the same general epilogue), the fp8 slice (its scales), normalisation and resampling
+kernels.  Attention has its own exact tests: tests/test_gpu_attention_exact.py."""
 import contextlib
 import ctypes
 import functools
