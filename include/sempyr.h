@@ -380,7 +380,8 @@ int sp_bn_apply_upsample2_pair(const void* x, void* y, int32_t n, int32_t split,
 int sp_bn_apply_upsample2(const void* x, void* y, int32_t n, int32_t h, int32_t w_, int32_t c, const float* mean,
                           const float* invstd, const float* gamma, const float* beta, const float* emb,
                           const int64_t* cls, int32_t act, int32_t dtype, sp_stream_t stream);
-/* dy is the gradient w.r.t. the (activated) output; partials: 1024*2*c floats, c_tmp: 2*c floats of scratch.
+/* dy is the gradient w.r.t. the (activated) output; partials: 1024*2*c floats, c_tmp: 2*c floats of scratch.  Every sample owns
+ * floor(1024 / n) >= 1 of the 1024 partial rows [c][2], so 1 <= n <= 1024 (SP_ERR_INVALID otherwise, before any launch).
  * Parameter gradients: dgamma/dbeta [c] (plain) or demb [num_classes][2c] (conditional; zeroed by the call). */
 int sp_bn_backward(const void* dy, const void* x, void* dx, int32_t n, int64_t hw, int32_t c, const float* mean,
                    const float* invstd, const float* gamma, const float* beta, const float* emb, const int64_t* cls,

@@ -787,6 +787,8 @@ extern "C" int sp_bn_backward(const void* dy, const void* x, void* dx, int32_t n
                               float* dgamma, float* dbeta, float* demb, int32_t num_classes, int32_t dtype,
                               sp_stream_t stream) {
     SP_CHECK_ARG(dy && x && dx && mean && invstd && partials && c_tmp && c % 4 == 0, "sp_bn_backward: bad args");
+    // every sample writes at least one partial row: more samples than rows would run past the caller's 1024 * 2 * c floats
+    SP_CHECK_ARG(n > 0 && n <= BN_MAX_PARTS, "sp_bn_backward: 1 <= n <= %d samples (n=%d)", BN_MAX_PARTS, n);
     SP_CHECK_ARG(!emb || (cls && (!demb || num_classes > 0)), "sp_bn_backward: conditional mode needs class indices");
     SP_CHECK_ARG(!demb || n <= BN_EMB_MAXN, "sp_bn_backward: the conditional backward supports batches up to %d", BN_EMB_MAXN);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
