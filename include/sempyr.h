@@ -468,6 +468,43 @@ int sp_ingest_image(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, 
                     const float* shift3, int32_t dtype, sp_stream_t stream);
 int sp_ingest_image_bwd(const void* dy, int32_t cp, void* dsrc, int32_t c, int64_t pixels, const float* scale3,
                         int32_t dtype, sp_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable augmentation inside the ingest pass (Zhao et al. 2020, "DiffAugment").  The reference has NO counterpart: its
+ * discriminator sees the images as they are (model_wrapper.py:153-155,174).  Off unless a caller asks for it.
+ *
+ * One application takes one row u of 8 fp32 uniforms in [0, 1) per image (a DEVICE pointer, n x 8, decoded in the kernel: no host
+ * value depends on it) and `policy`, any OR of SP_AUG_COLOR / SP_AUG_TRANSLATION / SP_AUG_CUTOUT; a part that is left out is the
+ * identity.  Images are 3-channel, H x W.  Arithmetic is fp32 whatever the storage type.  Forward, in this order:
+ *   color        o = u0 - 0.5, s = 2 u1, k = u2 + 0.5
+ *                b = x + o                                        brightness
+ *                a = (b - m) s + m,  m = (b_0 + b_1 + b_2) / 3    saturation (per pixel, over the 3 channels)
+ *                e = (a - M) k + M,  M = sum(x) / (3 H W) + o     contrast; saturation keeps the per-pixel channel mean, so the mean
+ *                                                                 of a over (c, h, w) is the mean of the raw input plus o
+ *   translation  r_y = int(H / 8 + 0.5), t_y = min(int(floorf(u3 * float(2 r_y + 1))), 2 r_y) - r_y; t_x likewise from W and u4
+ *                (one fp32 multiply, then floor);  out[h, w] = e[h + t_y, w + t_x], 0 outside the frame
+ *   cutout       q_y = int(H / 2 + 0.5), n_y = H + 1 - (q_y % 2), c_y = min(int(floorf(u5 * float(n_y))), n_y - 1); the rows
+ *                [c_y - q_y / 2, c_y - q_y / 2 + q_y) (integer division) cut with [0, H); columns likewise from W and u6; the output
+ *                is 0 inside the window.  u7 is unused.
+ * Backward, for dy on the output:
+ *   g1[c, h, w] = dy[c, h - t_y, w - t_x] where that position is inside the frame and outside the window, else 0
+ *   Gm = sum(g1) / (3 H W);  g2 = k g1 + (1 - k) Gm  (every input pixel);  dx_c = s g2_c + (1 - s) (g2_0 + g2_1 + g2_2) / 3
+ *
+ * sp_augment_ingest stands where sp_ingest_image stands: the same source (any strides, fp32 or the compute type), the same
+ * destination (padded NHWC of cp channels in the compute type, padding channels zero); sp_augment_ingest_bwd stands where
+ * sp_ingest_image_bwd stands (padded dy -> NHWC gradient of pitch 3 in dy's type).  With SP_AUG_COLOR each is TWO launches: a
+ * statistics launch (forward: sums of x; backward: sums of g1 over the 3 real channels of dy) that writes one fp32 partial per
+ * slice of an image into `partials` (n x sp_augment_slices() floats, no initialisation needed), and the apply launch, which adds
+ * an image's partials in slice order - no float atomics, bit-identical from run to run.  Without SP_AUG_COLOR: one launch, pure
+ * data movement, `partials` may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SP_AUG_COLOR = 1, SP_AUG_TRANSLATION = 2, SP_AUG_CUTOUT = 4 };
+/* partials per image of the statistics launch (backward != 0: of sp_augment_ingest_bwd); host-only */
+int sp_augment_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out);
+int sp_augment_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                      int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
+                      int32_t dtype, sp_stream_t stream);
+int sp_augment_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                          int32_t policy, float* partials, int32_t dtype, sp_stream_t stream);
 int sp_mask_concat(const void* feat, const float* mask, void* out, int64_t pixels, int32_t c, int32_t cp,
                    int32_t dtype, sp_stream_t stream);
 int sp_mask_mul_2d(const void* feat, int32_t ldf, const float* mask, void* out, int32_t ldo, int32_t batch,

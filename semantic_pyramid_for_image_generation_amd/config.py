@@ -35,6 +35,9 @@ results beyond floating-point summation order.  The kernel library itself reads 
                                                           (inception.InceptionV3Features); empty = validate() returns nan
     g_ema                 SP_G_EMA               0        decay of an exponential moving average of the generator's parameters (optim.ParameterEMA) that ModelWrapper
                                                           keeps, evaluates (validate / inference) and saves; 0 = off: no launch, no allocation, no checkpoint key
+    augment               SP_AUGMENT             ""       differentiable augmentation of every image the discriminator sees, inside its ingest pass (csrc/augment.hip,
+                                                          DESIGN.md 11): a comma-separated subset of color, translation, cutout; empty = off: no draw, no launch,
+                                                          no allocation (the one switch here that DOES change results: it is part of the training recipe)
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -76,6 +79,7 @@ class Config:
     defer_wgrad_reduce: bool = True
     inception_weights: str = ""
     g_ema: float = 0.0
+    augment: str = ""
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -91,7 +95,8 @@ class Config:
                    fuse_tail_grad=_flag("SP_FUSE_TAIL_GRAD", True), vgg_fc_joint=_flag("SP_VGG_FC_JOINT", True),
                    sn_skip_pack=_flag("SP_SN_SKIP_PACK", True), bn_pair=_flag("SP_BN_PAIR", True),
                    bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True),
-                   inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0))
+                   inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0),
+                   augment=os.environ.get("SP_AUGMENT", ""))
 
 
 CFG = Config.from_env()

@@ -1,0 +1,299 @@
+// Differentiable augmentation of the discriminator's input images inside the ingest pass (Zhao et al. 2020, "DiffAugment").
+// The reference has no counterpart.  These kernels REPLACE sp_ingest_image / sp_ingest_image_bwd (eltwise.hip) where a caller arms
+// them: same source, same padded NHWC destination, the transform applied on the way.
+//
+// THE TRANSFORM (stated once here and in DESIGN.md section 11; include/sempyr.h repeats it for the ABI's reader).
+// One row u of 8 fp32 uniforms in [0, 1) per image; policy = any subset of color / translation / cutout, a part left out is the
+// identity; 3-channel H x W images; fp32 arithmetic whatever the storage type.  Forward, in this order:
+//   color        o = u0 - 0.5, s = 2 u1, k = u2 + 0.5
+//                b = x + o;  a = (b - m) s + m, m = (b_0 + b_1 + b_2) / 3;  e = (a - M) k + M, M = sum(x) / (3 H W) + o
+//                (saturation keeps the per-pixel channel mean, so ONE reduction of the raw input gives the contrast's mean)
+//   translation  r_y = int(H / 8 + 0.5), t_y = min(int(floorf(u3 * float(2 r_y + 1))), 2 r_y) - r_y; t_x from W and u4
+//                out[h, w] = e[h + t_y, w + t_x], 0 outside the frame
+//   cutout       q_y = int(H / 2 + 0.5), n_y = H + 1 - (q_y % 2), c_y = min(int(floorf(u5 * float(n_y))), n_y - 1); rows
+//                [c_y - q_y / 2, c_y - q_y / 2 + q_y) cut with [0, H) are zeroed, columns likewise from W and u6; u7 is unused
+// Backward:  g1[c, h, w] = dy[c, h - t_y, w - t_x] where that position is inside the frame and outside the window, else 0;
+//            Gm = sum(g1) / (3 H W);  g2 = k g1 + (1 - k) Gm;  dx_c = s g2_c + (1 - s) (g2_0 + g2_1 + g2_2) / 3.
+//
+// LAUNCHES.  With color, two per application and direction: a statistics launch - grid (slices, images), 16-byte loads, wave-64
+// shuffle + LDS block sum, ONE fp32 partial per block - and the apply launch - grid (blocks, images), which adds its image's
+// partials in slice order (no float atomics: bit-identical from run to run).  Without color: the apply launch alone, which then only
+// moves data.  u is read and decoded on the device, so a captured graph replays with whatever the buffer holds.
+#include "common.h"
+
+namespace {
+
+constexpr int AUG_FWD_SLICE = 8192;      // source elements (of the 3 H W of an image) per statistics block, forward
+constexpr int AUG_BWD_SLICE = 2048;      // dy pixels per statistics block, backward
+constexpr int AUG_APPLY_BLOCKS = 128;    // apply blocks per image at most (grid-stride beyond)
+
+// what depends on the map size alone (host)
+struct AugGeom { int H, W, ry, rx, qy, qx, ny, nx; };
+
+inline AugGeom aug_geom(int h, int w) {
+    AugGeom g;
+    g.H = h; g.W = w;
+    g.ry = (int)((float)h / 8.f + 0.5f); g.rx = (int)((float)w / 8.f + 0.5f);
+    g.qy = (int)((float)h / 2.f + 0.5f); g.qx = (int)((float)w / 2.f + 0.5f);
+    g.ny = h + 1 - (g.qy % 2); g.nx = w + 1 - (g.qx % 2);
+    return g;
+}
+
+// one image's decoded row of u; the window is [y0, y1) x [x0, x1) in OUTPUT coordinates (empty without cutout)
+struct AugImage { float o, s, k; int ty, tx, y0, y1, x0, x1; };
+
+__device__ __forceinline__ AugImage aug_decode(const float* __restrict__ u, int policy, const AugGeom& g) {
+    AugImage a;
+    a.o = 0.f; a.s = 1.f; a.k = 1.f;
+    a.ty = a.tx = 0;
+    a.y0 = a.y1 = a.x0 = a.x1 = 0;
+    if (policy & SP_AUG_COLOR) { a.o = u[0] - 0.5f; a.s = 2.f * u[1]; a.k = u[2] + 0.5f; }
+    if (policy & SP_AUG_TRANSLATION) {
+        a.ty = min((int)floorf(u[3] * (float)(2 * g.ry + 1)), 2 * g.ry) - g.ry;
+        a.tx = min((int)floorf(u[4] * (float)(2 * g.rx + 1)), 2 * g.rx) - g.rx;
+    }
+    if (policy & SP_AUG_CUTOUT) {
+        const int cy = min((int)floorf(u[5] * (float)g.ny), g.ny - 1);
+        const int cx = min((int)floorf(u[6] * (float)g.nx), g.nx - 1);
+        a.y0 = cy - g.qy / 2; a.y1 = a.y0 + g.qy;
+        a.x0 = cx - g.qx / 2; a.x1 = a.x0 + g.qx;
+    }
+    return a;
+}
+
+// output position (h, w) shows source pixel (h + ty, w + tx): false where that is outside the frame or (h, w) is in the window
+__device__ __forceinline__ bool aug_live(const AugImage& a, const AugGeom& g, int h, int w) {
+    const int hs = h + a.ty, ws = w + a.tx;
+    return hs >= 0 && hs < g.H && ws >= 0 && ws < g.W && !(h >= a.y0 && h < a.y1 && w >= a.x0 && w < a.x1);
+}
+
+// an image's partials, added in slice order by every thread alike (a handful of floats; the loads are wave-uniform)
+__device__ __forceinline__ float aug_total(const float* __restrict__ partials, int n, int nsl) {
+    float t = 0.f;
+    for (int i = 0; i < nsl; ++i) t += partials[(long)n * nsl + i];
+    return t;
+}
+
+template <typename T> struct Vec16 { static constexpr int N = 16 / (int)sizeof(T); };
+
+// ---- statistics, forward: partial sums of the raw source --------------------------------------------
+// dense: the image's 3 H W elements are one contiguous, 16-byte aligned run (NCHW-contiguous or channels-last): 16-byte loads.
+template <typename TS>
+__global__ __launch_bounds__(256) void aug_stats_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw, int H, int W,
+                                                            int dense, float* __restrict__ partials) {
+    __shared__ float red[4];
+    constexpr int V = Vec16<TS>::N;
+    const int n = blockIdx.y;
+    const long total = 3L * H * W;
+    const long beg = (long)blockIdx.x * AUG_FWD_SLICE;
+    const long end = beg + AUG_FWD_SLICE < total ? beg + AUG_FWD_SLICE : total;
+    const TS* base = src + (long)n * sn;
+    float acc = 0.f;
+    if (dense) {
+        const long nvec = (end - beg) / V;
+        for (long i = threadIdx.x; i < nvec; i += 256) {
+            float v[V];
+            VecIO<TS, V>::ld(base + beg + i * V, v);
+#pragma unroll
+            for (int r = 0; r < V; ++r) acc += v[r];
+        }
+        for (long i = beg + nvec * V + threadIdx.x; i < end; i += 256) acc += Elem<TS>::ld(base + i);
+    } else {
+        const long HW = (long)H * W;
+        for (long i = beg + threadIdx.x; i < end; i += 256) {
+            const int c = (int)(i / HW);
+            const int r = (int)(i - c * HW);
+            const int h = r / W, w = r - h * W;
+            acc += Elem<TS>::ld(base + c * sc + h * sh + w * sw);
+        }
+    }
+    acc = block_sum_256(acc, red);
+    if (threadIdx.x == 0) partials[(long)n * gridDim.x + blockIdx.x] = acc;
+}
+
+// ---- apply, forward: what ingest_kernel does, through the transform ----------------------------------
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw,
+                                                            TD* __restrict__ dst, AugGeom g, int CP, const float* __restrict__ u,
+                                                            int policy, const float* __restrict__ partials, int nsl) {
+    const int n = blockIdx.y;
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
+    const int HW = g.H * g.W;
+    const bool color = (policy & SP_AUG_COLOR) != 0;
+    float M = 0.f;
+    if (color) M = aug_total(partials, n, nsl) / (float)(3 * HW) + a.o;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+        const int h = p / g.W, w = p - h * g.W;
+        float e[3] = {0.f, 0.f, 0.f};
+        if (aug_live(a, g, h, w)) {
+            const TS* s = src + (long)n * sn + (long)(h + a.ty) * sh + (long)(w + a.tx) * sw;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc);
+            if (color) {
+                float b[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) b[c] = e[c] + a.o;
+                const float m = (b[0] + b[1] + b[2]) / 3.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float sat = (b[c] - m) * a.s + m;
+                    e[c] = (sat - M) * a.k + M;
+                }
+            }
+        }
+        TD* d = dst + ((long)n * HW + p) * CP;
+        if (CP == 4) {
+            const float v[4] = {e[0], e[1], e[2], 0.f};
+            VecIO<TD, 4>::st(d, v);
+        } else if (sizeof(TD) == 2 && CP == 8) {
+            const float v[8] = {e[0], e[1], e[2], 0.f, 0.f, 0.f, 0.f, 0.f};
+            VecIO<bf16, 8>::st(reinterpret_cast<bf16*>(d), v);
+        } else {
+            for (int c = 0; c < CP; ++c) Elem<TD>::st(d + c, c < 3 ? e[c] : 0.f);
+        }
+    }
+}
+
+// the 3 real channels of one padded dy pixel (one 16-byte load where the pitch is 16 bytes)
+template <typename T>
+__device__ __forceinline__ void aug_ld3(const T* __restrict__ p, int CP, float (&v)[3]) {
+    constexpr int V = Vec16<T>::N;
+    if (CP == V) {
+        float t[V];
+        VecIO<T, V>::ld(p, t);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = Elem<T>::ld(p + c);
+    }
+}
+
+// ---- statistics, backward: partial sums of g1 = the dy values that reach an input pixel --------------
+template <typename T>
+__global__ __launch_bounds__(256) void aug_stats_bwd_kernel(const T* __restrict__ dy, int CP, AugGeom g, const float* __restrict__ u,
+                                                            int policy, float* __restrict__ partials) {
+    __shared__ float red[4];
+    const int n = blockIdx.y;
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
+    const int HW = g.H * g.W;
+    const int beg = blockIdx.x * AUG_BWD_SLICE;
+    const int end = beg + AUG_BWD_SLICE < HW ? beg + AUG_BWD_SLICE : HW;
+    float acc = 0.f;
+    for (int p = beg + threadIdx.x; p < end; p += 256) {
+        const int h = p / g.W, w = p - h * g.W;
+        if (aug_live(a, g, h, w)) {
+            float v[3];
+            aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
+            acc += (v[0] + v[1]) + v[2];
+        }
+    }
+    acc = block_sum_256(acc, red);
+    if (threadIdx.x == 0) partials[(long)n * gridDim.x + blockIdx.x] = acc;
+}
+
+// ---- apply, backward: padded dy -> NHWC gradient of pitch 3 (what ingest_bwd_kernel writes) ------------
+template <typename T>
+__global__ __launch_bounds__(256) void aug_apply_bwd_kernel(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, AugGeom g,
+                                                            const float* __restrict__ u, int policy, const float* __restrict__ partials,
+                                                            int nsl) {
+    const int n = blockIdx.y;
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
+    const int HW = g.H * g.W;
+    const bool color = (policy & SP_AUG_COLOR) != 0;
+    float Gm = 0.f;
+    if (color) Gm = aug_total(partials, n, nsl) / (float)(3 * HW);
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+        const int h = p / g.W, w = p - h * g.W;
+        const int ho = h - a.ty, wo = w - a.tx;      // the output position that shows this input pixel
+        float v[3] = {0.f, 0.f, 0.f};
+        if (ho >= 0 && ho < g.H && wo >= 0 && wo < g.W && !(ho >= a.y0 && ho < a.y1 && wo >= a.x0 && wo < a.x1))
+            aug_ld3(dy + ((long)n * HW + (long)ho * g.W + wo) * CP, CP, v);
+        if (color) {
+            float g2[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g2[c] = a.k * v[c] + (1.f - a.k) * Gm;
+            const float m = (g2[0] + g2[1] + g2[2]) / 3.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = a.s * g2[c] + (1.f - a.s) * m;
+        }
+        T* d = dsrc + ((long)n * HW + p) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+    }
+}
+
+inline int aug_slices(int h, int w, bool backward) {
+    return backward ? sp_div_up((long)h * w, AUG_BWD_SLICE) : sp_div_up(3L * h * w, AUG_FWD_SLICE);
+}
+inline int aug_apply_blocks(int h, int w) {
+    const int b = sp_div_up((long)h * w, 256);
+    return b < AUG_APPLY_BLOCKS ? b : AUG_APPLY_BLOCKS;
+}
+// 3 H W <= 2^24: float(3 H W) is exact, and pixel indices fit an int with room to spare
+inline bool aug_dims_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && 3L * h * w <= (1L << 24); }
+
+template <typename TS, typename TD>
+void aug_launch_fwd(const void* src, long sn, long sc, long sh, long sw, void* dst, int n, const AugGeom& g, int cp, const float* u,
+                    int policy, float* partials, hipStream_t s) {
+    int nsl = 0;
+    if (policy & SP_AUG_COLOR) {
+        nsl = aug_slices(g.H, g.W, false);
+        const bool run = (sw == 1 && sh == g.W && sc == (long)g.H * g.W) || (sc == 1 && sw == 3 && sh == 3L * g.W);
+        const int dense = run && reinterpret_cast<uintptr_t>(src) % 16 == 0 && (sn * (long)sizeof(TS)) % 16 == 0;
+        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw, g.H, g.W, dense, partials);
+    }
+    hipLaunchKernelGGL((aug_apply_fwd_kernel<TS, TD>), dim3(aug_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw,
+                       (TD*)dst, g, cp, u, policy, partials, nsl);
+}
+
+template <typename T>
+void aug_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g, const float* u, int policy, float* partials, hipStream_t s) {
+    int nsl = 0;
+    if (policy & SP_AUG_COLOR) {
+        nsl = aug_slices(g.H, g.W, true);
+        hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, n), dim3(256), 0, s, (const T*)dy, cp, g, u, policy, partials);
+    }
+    hipLaunchKernelGGL(aug_apply_bwd_kernel<T>, dim3(aug_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const T*)dy, cp, (T*)dsrc, g, u, policy,
+                       partials, nsl);
+}
+
+}  // namespace
+
+extern "C" int sp_augment_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out) {
+    SP_CHECK_ARG(slices_out && aug_dims_ok(1, h, w_), "sp_augment_slices: bad args (h=%d w=%d)", h, w_);
+    *slices_out = aug_slices(h, w_, backward != 0);
+    return SP_OK;
+}
+
+extern "C" int sp_augment_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                                 int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
+                                 int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(src && dst && u && cp >= 3, "sp_augment_ingest: bad args");
+    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_ingest: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
+    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "sp_augment_ingest: bad dtype");
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_ingest: bad policy %d", policy);
+    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_ingest: the color policy needs the partials buffer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const AugGeom g = aug_geom(h, w_);
+    if (src_dtype == SP_F32 && dtype == SP_F32) aug_launch_fwd<float, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
+    else if (src_dtype == SP_F32 && dtype == SP_BF16) aug_launch_fwd<float, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
+    else if (src_dtype == SP_BF16 && dtype == SP_BF16) aug_launch_fwd<bf16, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
+    else aug_launch_fwd<bf16, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_augment_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                                     int32_t policy, float* partials, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(dy && dsrc && u && cp >= 3, "sp_augment_ingest_bwd: bad args");
+    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_ingest_bwd: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
+    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_augment_ingest_bwd: bad dtype");
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_ingest_bwd: bad policy %d", policy);
+    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_ingest_bwd: the color policy needs the partials buffer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const AugGeom g = aug_geom(h, w_);
+    if (dtype == SP_F32) aug_launch_bwd<float>(dy, cp, dsrc, n, g, u, policy, partials, s);
+    else aug_launch_bwd<bf16>(dy, cp, dsrc, n, g, u, policy, partials, s);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}

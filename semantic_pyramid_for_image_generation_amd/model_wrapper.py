@@ -16,6 +16,9 @@ PNG (misc.save_image_grid - torchvision is not a dependency).
 Beyond the reference: with ``generator_ema`` (or SP_G_EMA) an exponential moving average of the generator's parameters is kept on the
 device (optim.ParameterEMA), updated behind every generator optimizer step, swapped in for ``validate`` / ``inference`` and saved
 beside the four reference keys of a checkpoint.  Off by default: nothing of it runs then.
+Likewise ``augment`` (or SP_AUGMENT): differentiable augmentation - color, translation, cutout - of every image the discriminator
+sees, applied inside its ingest pass (csrc/augment.hip): three independent transforms per step from one
+(3, B, 8) draw of uniforms made in front of the latents.  Off by default: no draw, no launch, no allocation.
 """
 from __future__ import annotations
 
@@ -52,7 +55,8 @@ class ModelWrapper(object):
                  save_data_path: Optional[str] = 'saved_data',
                  gradient_reducer=None,
                  inception=None,
-                 generator_ema=None) -> None:
+                 generator_ema=None,
+                 augment=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -96,6 +100,16 @@ class ModelWrapper(object):
                 generator_ema = optim.ParameterEMA(self.generator, decay=float(generator_ema))
             self.generator_ema = generator_ema
             self.logger.hyperparameter['generator_ema'] = str({"decay": self.generator_ema.decay, "warmup": self.generator_ema.warmup})
+        # augment: "color,translation,cutout" or a subset; None: CFG.augment (SP_AUGMENT - main.py's fixed keywords again); "" = off.
+        # Fixed for the wrapper's life.  _aug_policy is the bit mask of ops.augment_policy (0 = off: nothing below ever runs).
+        if augment is None:
+            augment = CFG.augment
+        self._aug_policy = ops.augment_policy(augment)
+        if self._aug_policy:
+            if not isinstance(self.discriminator, Discriminator):
+                raise ops.L.SempyrError("augment: the transform runs inside this package's Discriminator's ingest pass; a caller's own "
+                                        "discriminator module cannot be armed")
+            self.logger.hyperparameter['augment'] = ",".join(w for w, bit in ops._AUG_WORDS.items() if self._aug_policy & bit)
         self._d_params = [p for p in self.discriminator.parameters()]
         self._g_params = [p for p in self.generator.parameters()]
         # every gradient of a network lives in ONE flat fp32 buffer (ops.SpectralNormBank.flat; param.grad are views of it):
@@ -218,10 +232,36 @@ class ModelWrapper(object):
         data parallelism the discriminator's gradient all-reduce then hides behind _g_features instead of the generator forward.)"""
         return CFG.g_pair and isinstance(self.generator, Generator) and self.generator.training
 
-    def _d_phase(self, images_real, labels, labels_f, masks, noise_d, features_real=None, noise_g=None):
+    def _augment_rows(self, images_real, augment_u):
+        """The step's (3, B, 8) uniforms - row 0: the real images of the D step, 1: its fake images, 2: the fake images of the G step in
+        front of D - or None with augmentation off.  Drawn FIRST in a step (before the latents) unless the caller brings them."""
+        if not self._aug_policy:
+            if augment_u is not None:
+                raise ops.L.SempyrError("augment_u given, but this ModelWrapper augments nothing (augment / SP_AUGMENT)")
+            return None
+        shape = (3, images_real.shape[0], 8)
+        if augment_u is None:
+            return torch.rand(shape, dtype=torch.float32, device=images_real.device)
+        if tuple(augment_u.shape) != shape:
+            raise ops.L.SempyrError("augment_u must be %s (three transforms x batch x 8 uniforms), got %s" % (shape, tuple(augment_u.shape)))
+        return augment_u.detach().to(device=images_real.device, dtype=torch.float32).contiguous()
+
+    def _d_call(self, fn, rows, *args):
+        """fn(*args) - the discriminator's forward or forward_pair - armed with these rows of uniforms for that one call (None: as it is)."""
+        if rows is None:
+            return fn(*args)
+        D = self.discriminator
+        D._augment = (self._aug_policy,) + tuple(rows)
+        try:
+            return fn(*args)
+        finally:
+            D._augment = None
+
+    def _d_phase(self, images_real, labels, labels_f, masks, noise_d, features_real=None, noise_g=None, aug_u=None):
         """model_wrapper.py:136-160: forward passes and backward of the discriminator step (everything but Adam).  features_real: the
         pyramid of images_real where an earlier generator step has already computed it (_g_rest, next_images_real).  noise_g: the
-        latents of the generator step, for the case that its forward is taken in the same pass as this step's (_g_pair_ok)."""
+        latents of the generator step, for the case that its forward is taken in the same pass as this step's (_g_pair_ok).  aug_u: the
+        step's uniforms (_augment_rows) - D sees T(real; aug_u[0]) and T(fake; aug_u[1]); the generator and the VGG-16 see the images."""
         G, D, V = self.generator, self.discriminator, self.vgg16
         G.zero_grad()
         D.zero_grad()
@@ -242,10 +282,11 @@ class ModelWrapper(object):
                 G.map_mode = "stash"                  # this forward and the G step's see the same pyramid, masks and weights
             images_fake = G(input=noise_d, features=features_real, masks=masks, class_id=labels_f)
         if CFG.d_pair and hasattr(D, "forward_pair") and D.training and images_fake.shape == images_real.shape:
-            prediction_real, prediction_fake = D.forward_pair(images_real, images_fake, labels)     # one trunk pass over 2B images
+            rows = None if aug_u is None else (aug_u[0], aug_u[1])
+            prediction_real, prediction_fake = self._d_call(D.forward_pair, rows, images_real, images_fake, labels)     # one trunk pass over 2B images
         else:
-            prediction_real = D(images_real, labels)
-            prediction_fake = D(images_fake, labels)
+            prediction_real = self._d_call(D, None if aug_u is None else (aug_u[0],), images_real, labels)
+            prediction_fake = self._d_call(D, None if aug_u is None else (aug_u[1],), images_fake, labels)
         loss_d_real, loss_d_fake = self.discriminator_loss(prediction_real, prediction_fake)
         self._arm_reducer("d")
         # d(real + fake): one seed per loss instead of a sum kernel and autograd's own seed (model_wrapper.py:158-160)
@@ -298,8 +339,9 @@ class ModelWrapper(object):
         return loss_div, features_fake, features_next
 
     def _g_rest(self, images_fake, noise_g, labels, masks, features_real, w_rec, w_div, next_images_real=None, features_next_out=None,
-                ahead=None):
-        """model_wrapper.py:174-188: D(fake), the generator and reconstruction losses, backward (everything but Adam).  ahead: what
+                ahead=None, aug_u=None):
+        """model_wrapper.py:174-188: D(fake), the generator and reconstruction losses, backward (everything but Adam).  aug_u: the step's
+        uniforms - D sees T(fake; aug_u[2]), whose backward carries D's image gradient through T; every other loss sees the images.  ahead: what
         _g_features has already computed for these fake images (train_step: in front of the discriminator's optimizer step); without
         it that part runs here.  features_next_out: static tensors to copy the next batch's pyramid into after the backward pass
         (captured graphs); it is kept in self._vgg_ahead."""
@@ -311,7 +353,7 @@ class ModelWrapper(object):
         for p in self._d_params:                               # dead D weight gradients are skipped
             p.requires_grad_(False)
         try:
-            prediction_fake = D(images_fake, labels)
+            prediction_fake = self._d_call(D, None if aug_u is None else (aug_u[2],), images_fake, labels)
             loss_g = self.generator_loss(prediction_fake)
             if isinstance(self.semantic_reconstruction_loss, SemanticReconstructionLoss):
                 loss_rec = self.semantic_reconstruction_loss(features_real, features_fake, masks, weight=w_rec)
@@ -348,10 +390,10 @@ class ModelWrapper(object):
 
     def train_step(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1,
                    noise_d: Optional[torch.Tensor] = None, noise_g: Optional[torch.Tensor] = None,
-                   next_images_real: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   next_images_real: Optional[torch.Tensor] = None, augment_u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """One iteration of model_wrapper.py:131-190 on tensors already on the device.  ``noise_d`` / ``noise_g``
-        replace the two ``torch.randn`` draws (model_wrapper.py:147,168) for parity runs.  Returns the loss
-        scalars as device tensors (no host sync).
+        replace the two ``torch.randn`` draws (model_wrapper.py:147,168) for parity runs, ``augment_u`` ((3, B, 8), with augmentation
+        on only) the ``torch.rand`` draw in front of them.  Returns the loss scalars as device tensors (no host sync).
 
         ``next_images_real`` (optional): the real images of the NEXT call (the same tensor object must then be passed as its
         ``images_real``).  The frozen VGG-16 sees them in the pass it makes over this iteration's fake images - one pass over 2B
@@ -368,9 +410,10 @@ class ModelWrapper(object):
         idx = _class_index(labels)
         labels = idx if isinstance(self.discriminator, Discriminator) else raw_labels
         labels_f = idx if isinstance(self.generator, Generator) else raw_labels
+        aug_u = self._augment_rows(images_real, augment_u)
         with profiling.range("D phase"):
             features_real, loss_d_real, loss_d_fake = self._d_phase(images_real, labels, labels_f, masks, noise_d,
-                                                                      self._features_ahead(images_real), noise_g)
+                                                                      self._features_ahead(images_real), noise_g, aug_u)
             self._start_reduce("d", self._d_params, eager=True)
         with profiling.range("G forward"):
             images_fake, noise_g = self._g_forward(images_real, labels_f, masks, features_real, noise_g)
@@ -380,7 +423,7 @@ class ModelWrapper(object):
             self._optimizer_step("d", self.discriminator_optimizer)
         with profiling.range("G rest"):
             loss_g, loss_rec, loss_div = self._g_rest(images_fake, noise_g, labels, masks, features_real, w_rec, w_div, next_images_real,
-                                                      ahead=ahead)
+                                                      ahead=ahead, aug_u=aug_u)
             self._start_reduce("g", self._g_params, eager=True)
         with profiling.range("Adam(G)"):
             self._join_reduce("g")
@@ -416,6 +459,9 @@ class ModelWrapper(object):
         zdim = (images_real.shape[0], self.latent_dimensions)
         st["noise_d"] = torch.zeros(zdim, dtype=torch.float32, device=images_real.device)
         st["noise_g"] = torch.zeros(zdim, dtype=torch.float32, device=images_real.device)
+        # the step's uniforms of the augmentation: a static buffer the transform launches INSIDE the graphs decode on the device;
+        # train_step_graphed refills it in front of every replay (None with augmentation off: no buffer, no draw)
+        st["augment_u"] = torch.zeros((3, zdim[0], 8), dtype=torch.float32, device=images_real.device) if self._aug_policy else None
         # The pyramid of the real images is computed AHEAD (config.CFG.vgg_pair): the generator-step graph takes the next batch's real
         # images (st["images_next"]) through the VGG pass it makes over the fake images and leaves their features in st["feats_real"],
         # which the discriminator-step graph of the next replay reads.  Eager once here, so that the first replay finds them.
@@ -443,7 +489,8 @@ class ModelWrapper(object):
                 cls = st["cls"] = _class_index(st["labels"])          # recomputed by every replay of this graph; the other two read it
                 lab_d = cls if isinstance(self.discriminator, Discriminator) else st["labels"]      # (a caller's own module gets what it was written for)
                 lab_g = cls if isinstance(self.generator, Generator) else st["labels"]
-                feats, l_real, l_fake = self._d_phase(st["images"], lab_d, lab_g, st["masks"], st["noise_d"], st["feats_real"], st["noise_g"])
+                feats, l_real, l_fake = self._d_phase(st["images"], lab_d, lab_g, st["masks"], st["noise_d"], st["feats_real"], st["noise_g"],
+                                                      st["augment_u"])
             st["d_grads"] = [p.grad for p in self._d_params]
             # second graph: what the generator step can do in front of the discriminator's optimizer step - its forward, unless that rode
             # in the discriminator phase's pass (Generator.forward_pair), the diversity loss and the VGG-16 pass over the fake images
@@ -455,7 +502,7 @@ class ModelWrapper(object):
             gg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gg, pool=gd.pool()):
                 l_g, l_rec, l_div = self._g_rest(fake, st["noise_g"], lab_d, st["masks"], feats, w_rec, w_div, st.get("images_next"),
-                                                 st["feats_real"], ahead=ahead)
+                                                 st["feats_real"], ahead=ahead, aug_u=st["augment_u"])
             st["g_grads"] = [p.grad for p in self._g_params]
         except BaseException:
             ops.drop_wgrad_reduce()            # queued slab reductions of the abandoned capture point into its (released) pool
@@ -487,7 +534,7 @@ class ModelWrapper(object):
 
     def train_step_graphed(self, images_real: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, masks=None,
                            noise_d: Optional[torch.Tensor] = None, noise_g: Optional[torch.Tensor] = None,
-                           next_images_real: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                           next_images_real: Optional[torch.Tensor] = None, augment_u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """train_step() through the captured graphs (capture_graphs() first).  images / labels / masks: new batch to copy into
         the graphs' static inputs, or None to reuse the resident one.  next_images_real: as in train_step() - the next call's real
         images, whose VGG pyramid this call computes ahead; without it (and outside the resident mode) the next call computes its
@@ -498,6 +545,12 @@ class ModelWrapper(object):
             self._graph_state = None
             raise RuntimeError("train_step_graphed(): the networks' flat gradient buffers were re-allocated after capture_graphs() "
                                "(parameters or compute dtype changed) - capture again")
+        if st.get("augment_u") is None:
+            self._augment_rows(st["images"], augment_u)         # (augmentation off: raises if the caller brings uniforms)
+        elif augment_u is None:
+            st["augment_u"].uniform_()                          # first, as train_step() draws: the same RNG stream
+        else:
+            st["augment_u"].copy_(self._augment_rows(st["images"], augment_u))
         if noise_d is None:
             st["noise_d"].normal_()
         else:

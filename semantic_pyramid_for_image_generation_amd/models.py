@@ -751,6 +751,17 @@ class Discriminator(nn.Module):
         self.embedding = SNEmbedding(number_of_classes, 128)
         self.apply(init_weights)
         self._bank = ops.SpectralNormBank(_collect_sn(self), _non_sn_params(self))
+        # Differentiable augmentation (csrc/augment.hip; beyond the reference): ModelWrapper arms ONE call by setting this to
+        # (policy mask, u) for forward or (policy mask, u_a, u_b) for forward_pair and clears it behind the call.  None: the plain ingest.
+        self._augment = None
+
+    def _ingest(self, input: torch.Tensor, dt) -> torch.Tensor:
+        aug = getattr(self, "_augment", None)
+        if aug is None:
+            return ops.ingest_image(input, dt)
+        if len(aug) != 2:
+            raise ops.L.SempyrError("Discriminator.forward: armed for forward_pair (two rows of uniforms)")
+        return ops.augment_ingest_image(input, dt, aug[1], aug[0])
 
     def forward(self, input: torch.Tensor, class_id: torch.Tensor) -> torch.Tensor:
         dt = ops.compute_dtype()
@@ -758,7 +769,7 @@ class Discriminator(nn.Module):
         self._bank.begin(self.training, dt, input.device)
         try:
             L = self.layers
-            x = L[0](ops.ingest_image(input, dt))
+            x = L[0](self._ingest(input, dt))
             if _COMMUTE_1X1 and _FUSE_ACT_POOL:
                 # every block forms lrelu(x) and avgpool(x) of its own input in one pass (ops.act_avgpool2)
                 x = L[3](L[2](L[1](x)))
@@ -790,8 +801,20 @@ class Discriminator(nn.Module):
         separate calls up to fp32 rounding of the scale; no image gradients (the D step needs none)."""
         dt = ops.compute_dtype()
         ops.require_gpu(input_a)
+        aug = getattr(self, "_augment", None)
+        if aug is not None and len(aug) != 3:
+            raise ops.L.SempyrError("Discriminator.forward_pair: armed for forward (one row of uniforms)")
         if not (_COMMUTE_1X1 and _FUSE_ACT_POOL):
-            return self(input_a, class_id), self(input_b, class_id)
+            if aug is None:
+                return self(input_a, class_id), self(input_b, class_id)
+            try:
+                out = []
+                for img, u in ((input_a, aug[1]), (input_b, aug[2])):
+                    self._augment = (aug[0], u)
+                    out.append(self(img, class_id))
+                return out[0], out[1]
+            finally:
+                self._augment = aug
         bank = self._bank
         na = input_a.shape[0]
         if getattr(self, "_trunk_slots", None) is None:      # every convolution runs on forward a's packing in the two-group pass
@@ -799,7 +822,11 @@ class Discriminator(nn.Module):
         pair = bank.begin_pair(self.training, dt, input_a.device, na, self._trunk_slots)
         try:
             L = self.layers
-            x = L[0](ops.ingest_image_pair(input_a, input_b, dt))
+            if aug is None:
+                x = ops.ingest_image_pair(input_a, input_b, dt)
+            else:
+                x = ops.augment_ingest_image_pair(input_a, input_b, dt, aug[1], aug[2], aug[0])
+            x = L[0](x)
             x = L[3](L[2](L[1](x)))
             x = L[7](L[6](L[5](L[4](x))))
             x = ops.adaptive_avgpool(x, 1, 1, ACT_LRELU).flatten(1)

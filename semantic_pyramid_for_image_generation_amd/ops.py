@@ -1735,6 +1735,148 @@ def ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, scale3=No
     return y
 
 
+# ---- differentiable augmentation inside the ingest pass (csrc/augment.hip; the transform is defined there and in DESIGN.md 11) ----
+AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
+_AUG_WORDS = {"color": AUG_COLOR, "translation": AUG_TRANSLATION, "cutout": AUG_CUTOUT}
+
+
+def augment_policy(policy) -> int:
+    """"color,translation,cutout" (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask of
+    include/sempyr.h's SP_AUG_*.  An unknown word raises."""
+    if policy is None:
+        return 0
+    if isinstance(policy, int) and not isinstance(policy, bool):
+        if not 0 <= policy <= 7:
+            raise L.SempyrError("augmentation policy mask %d: not an OR of color (1), translation (2), cutout (4)" % policy)
+        return policy
+    if not isinstance(policy, str):
+        raise L.SempyrError("augmentation policy: a comma-separated string of %s (got %r)" % (" / ".join(_AUG_WORDS), policy))
+    mask = 0
+    for word in policy.split(","):
+        word = word.strip()
+        if not word:
+            continue
+        if word not in _AUG_WORDS:
+            raise L.SempyrError("augmentation policy word %r: choose among %s" % (word, ", ".join(_AUG_WORDS)))
+        mask |= _AUG_WORDS[word]
+    return mask
+
+
+def augment_geometry(h: int, w: int):
+    """(r_y, r_x, q_y, q_x, n_y, n_x) of an h x w map: translation radius, cutout window size and number of cutout centres, with
+    the kernel's fp32 operations (csrc/augment.hip: aug_geom)."""
+    hw = torch.tensor([h, w], dtype=torch.float32)
+    ry, rx = (int(v) for v in (hw / 8.0 + 0.5).to(torch.int64))
+    qy, qx = (int(v) for v in (hw / 2.0 + 0.5).to(torch.int64))
+    return ry, rx, qy, qx, h + 1 - (qy % 2), w + 1 - (qx % 2)
+
+
+def augment_decode(u: torch.Tensor, h: int, w: int, policy=7):
+    """The kernel's decoding of `u` ((n, 8) uniforms in [0, 1)) for h x w images, on the host with the same fp32 operations:
+    (o, s, k, t_y, t_x, c_y, c_x), fp32 / int64 tensors of n entries.  A part the policy leaves out decodes to the identity
+    (o = 0, s = k = 1, t = 0); c_y / c_x mean nothing without cutout.  The cutout rows are [c_y - q_y // 2, c_y - q_y // 2 + q_y)
+    cut with [0, h), q_y from augment_geometry()."""
+    policy = augment_policy(policy)
+    u = u.detach().to("cpu", torch.float32)
+    if u.dim() != 2 or u.shape[1] != 8:
+        raise L.SempyrError("augment_decode: u must be (n, 8), got %s" % (tuple(u.shape),))
+    ry, rx, _, _, ny, nx = augment_geometry(h, w)
+    n = u.shape[0]
+    o, s, k = torch.zeros(n), torch.ones(n), torch.ones(n)
+    ty = tx = torch.zeros(n, dtype=torch.int64)
+    if policy & AUG_COLOR:
+        o, s, k = u[:, 0] - 0.5, 2.0 * u[:, 1], u[:, 2] + 0.5
+
+    def pick(col, count):          # min(int(floorf(u * float(count))), count - 1): one fp32 multiply, then floor
+        return torch.floor(u[:, col] * torch.tensor(float(count), dtype=torch.float32)).to(torch.int64).clamp(max=count - 1)
+    if policy & AUG_TRANSLATION:
+        ty, tx = pick(3, 2 * ry + 1) - ry, pick(4, 2 * rx + 1) - rx
+    cy, cx = pick(5, ny), pick(6, nx)
+    return o, s, k, ty, tx, cy, cx
+
+
+def _augment_args(img, u, policy):
+    require_gpu(img)
+    policy = augment_policy(policy)
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise L.SempyrError("the augmenting ingest takes 3-channel images (n, 3, h, w), got %s" % (tuple(img.shape),))
+    if not (u.is_cuda and u.dtype == torch.float32 and tuple(u.shape) == (img.shape[0], 8) and u.is_contiguous()):
+        raise L.SempyrError("the augmenting ingest takes u as a contiguous fp32 (n, 8) tensor on the GPU, one row per image (got %s %s for "
+                            "%d images)" % (tuple(u.shape), u.dtype, img.shape[0]))
+    return policy
+
+
+def augment_slices(h: int, w: int, backward: bool) -> int:
+    """Partials per image that the statistics launch of the augmenting ingest writes (include/sempyr.h: sp_augment_slices)."""
+    out = ctypes.c_int64(0)
+    L.call("sp_augment_slices", h, w, 1 if backward else 0, ctypes.byref(out))
+    return int(out.value)
+
+
+def _augment_partials(n, h, w, policy, backward, device):
+    if not policy & AUG_COLOR:
+        return None
+    return torch.empty((n, augment_slices(h, w, backward)), dtype=torch.float32, device=device)
+
+
+def _augment_fwd(img, y_ptr, dtype, cp, u, policy):
+    n, _, h, w = img.shape
+    sn, scs, sh, sw = img.stride()
+    part = _augment_partials(n, h, w, policy, False, img.device)
+    L.call("sp_augment_ingest", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(part),
+           sp_dtype(dtype), stream())
+
+
+class _AugmentIngestFn(torch.autograd.Function):
+    """_IngestFn with the augmentation applied in the same pass: T(img; u) -> NHWC with zero-padded channels; gradients flow through T."""
+
+    @staticmethod
+    def forward(ctx, img, dtype, u, policy):
+        n, c, h, w = img.shape
+        cp = pad_channels(c, dtype)
+        y = nhwc_empty(n, cp, h, w, dtype, img.device)
+        _augment_fwd(img, ptr(y), dtype, cp, u, policy)
+        ctx.cfg = (n, h, w, cp, policy, img.dtype)
+        ctx.u = u
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        n, h, w, cp, policy, src_dtype = ctx.cfg
+        dy = as_nhwc(dy)
+        dsrc = nhwc_empty(n, 3, h, w, dy.dtype, dy.device)
+        part = _augment_partials(n, h, w, policy, True, dy.device)
+        L.call("sp_augment_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), sp_dtype(dy.dtype), stream())
+        if dsrc.dtype != src_dtype:
+            dsrc = dsrc.to(src_dtype)
+        return dsrc, None, None, None
+
+
+def augment_ingest_image(img: torch.Tensor, dtype, u: torch.Tensor, policy) -> torch.Tensor:
+    """ingest_image(T(img; u), dtype) in the ingest's own pass (csrc/augment.hip): u = (n, 8) fp32 uniforms on the device, one row per
+    image, decoded in the kernel (augment_decode restates it); policy = "color,translation,cutout", a subset, or the bit mask."""
+    policy = _augment_args(img, u, policy)
+    return _AugmentIngestFn.apply(img, dtype, u, policy)
+
+
+def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u_a: torch.Tensor, u_b: torch.Tensor, policy) -> torch.Tensor:
+    """ingest_image_pair with each batch under its own transform: ONE padded NHWC batch [T(a; u_a) | T(b; u_b)], no autograd of
+    its own (the discriminator step needs no image gradient)."""
+    with torch.no_grad():
+        img_a, img_b = img_a.detach(), img_b.detach()
+        policy = _augment_args(img_a, u_a, policy)
+        _augment_args(img_b, u_b, policy)
+        na, c, h, w = img_a.shape
+        if tuple(img_b.shape[1:]) != (c, h, w):
+            raise L.SempyrError("augment_ingest_image_pair: image shapes differ (%s, %s)" % (tuple(img_a.shape), tuple(img_b.shape)))
+        cp = pad_channels(c, dtype)
+        y = nhwc_empty(na + img_b.shape[0], cp, h, w, dtype, img_a.device)
+        esz = y.element_size()
+        for img, u, off in ((img_a, u_a, 0), (img_b, u_b, na)):
+            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy)
+    return y
+
+
 def mask_concat(feat: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """cat(feat * mask, mask) with the channel count padded to a 16-byte multiple (models.py:94).  No autograd:
     the features come from the frozen VGG under no_grad and mask gradients are dead."""
