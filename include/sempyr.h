@@ -284,6 +284,13 @@ int sp_linear_wgrad(const void* x, int32_t ldx, const void* dy, int32_t ld_dy, f
  *   pack_blocks > 0: the packing kernel runs on a 1-D grid of exactly that many blocks and layer i owns blocks
  *   [pack_block0[i], pack_block0[i+1]) - ceil(cin_p/32)*ceil(cout_p/32) of them (kind 1: ceil(rows*cols/1024)).  The 2-D grid
  *   (pack_blocks == 0) launches max-tiles x n_layers blocks, 90 % of which exit at once for a network with one big layer.
+ *   pack_blocks == -1: nothing is packed (the power iteration and the snapshots only; the pack arena stays as it is) - a table
+ *   whose block ranges are ALL empty cannot be expressed with pack_blocks > 0.
+ *   Alignment (the table lives on the device, so only the two base pointers can be - and are - checked by the launcher; the
+ *   rest is the caller's contract): w, u, v of every layer, scratch and pack_arena are 16-byte aligned; scratch_off and part_off
+ *   are multiples of 4 floats (the forward reads and writes 16 bytes at a time wherever cols % 4 == 0; the batched backward
+ *   tests the alignment and falls back to scalar accesses); fwd_off and dgrad_off are multiples of 8 bytes.  n_layers <= 256.
+ *   taps <= 9 in every entry (the packing and the batched backward stage a 32- or 256-channel x taps tile in LDS sized for 9).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct sp_sn_layer {
     const float* w;        /* weight_orig viewed [rows][cols] (OIHW flattened, cols = cin*taps)   */
@@ -312,7 +319,10 @@ int sp_sn_pair_scales(const sp_sn_layer* table_dev, int32_t n_layers, const floa
  * included): the result is added to it - the gradients of a second forward through the same network (D(real) and D(fake),
  * model_wrapper.py:150-160) land on the first one's without one autograd addition per parameter.  bias_grads (NULL to
  * skip): the layers' bias-gradient slots of the arena are copied (accumulate_from == NULL) or added into it.
- * dot_partials: n_layers x 512 floats of scratch (no initialisation): per-block partial sums of <dW, W>, added in block order. */
+ * dot_partials: n_layers x 512 floats of scratch (no initialisation): per-block partial sums of <dW, W>, added in block order;
+ * layer i uses its first min(512, ceil(max_elems / 1024), ceil(rows * cols / 1024)) entries, the others are not touched.
+ * table_dev may point INTO a larger table (layers lo .. hi of it, n_layers = hi - lo): grad_off / bias_off keep addressing the
+ * whole of `grads` / `bias_grads`, and nothing outside the ranges of the layers given is written.  taps <= 9. */
 typedef struct sp_sn_bwd_layer {
     const float* w;        /* weight_orig [rows][cols] */
     int64_t dw_off, dot_off, scratch_off, grad_off;

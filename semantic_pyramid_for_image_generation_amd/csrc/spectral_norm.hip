@@ -503,7 +503,9 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, int rows, int co
 extern "C" int sp_sn_forward(const sp_sn_layer* table_dev, int32_t n_layers, int32_t max_rows, int32_t max_cols,
                              int64_t max_pack_elems, float* scratch, int64_t scratch_floats, void* pack_arena,
                              int32_t power_iter, int32_t dtype, int32_t pack_blocks, sp_stream_t stream) {
-    SP_CHECK_ARG(table_dev && scratch && pack_arena && pack_blocks >= 0, "sp_sn_forward: null pointer / negative pack_blocks");
+    SP_CHECK_ARG(table_dev && scratch && pack_arena && pack_blocks >= -1, "sp_sn_forward: null pointer / pack_blocks below -1");
+    SP_CHECK_ARG(((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(pack_arena)) & 15) == 0,
+                 "sp_sn_forward: scratch and pack_arena must be 16-byte aligned");
     SP_CHECK_ARG(n_layers > 0 && n_layers <= SN_MAX_LAYERS && max_rows > 0 && max_cols > 0 && max_pack_elems > 0, "sp_sn_forward: bad extents");
     SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_sn_forward: bad dtype %d", dtype);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -516,6 +518,7 @@ extern "C" int sp_sn_forward(const sp_sn_layer* table_dev, int32_t n_layers, int
     SP_LAUNCH_CHECK();
     hipLaunchKernelGGL(sn_finalize_kernel, dim3(n_layers), dim3(256), 0, s, table_dev, scratch, power_iter);
     SP_LAUNCH_CHECK();
+    if (pack_blocks < 0) return SP_OK;       // every layer's block range is empty: a 1-block flat grid would hand its block to the last layer
     dim3 pgrid(sp_div_up(max_pack_elems, 1024), n_layers);     // >= tiles of the largest layer (a tile holds >= 1024 packed elements)
     if (pack_blocks > 0) pgrid = dim3((unsigned)pack_blocks);
     const int flat = pack_blocks > 0 ? 1 : 0;

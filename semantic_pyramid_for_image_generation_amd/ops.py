@@ -604,8 +604,11 @@ class SpectralNormBank:
             if i not in skip:
                 blocks += width
         dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.table_dev.device)
-        cache[skip] = (dev, max(blocks, 1), self._table_host)
-        return dev, max(blocks, 1)
+        # every layer skipped: -1 = no packing launch at all (a grid of one block would be handed to the last layer, whose tile 0 it
+        # would write although that layer was skipped)
+        blocks = blocks if blocks > 0 else -1
+        cache[skip] = (dev, blocks, self._table_host)
+        return dev, blocks
 
     def begin(self, training: bool, dtype, device, skip_pack: Optional[frozenset] = None) -> SNCall:
         """skip_pack: slots of layers whose packed weights this forward will not be asked for (_unpacked_table)."""
