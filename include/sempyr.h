@@ -652,6 +652,36 @@ int sp_adam_multi_guarded(const sp_adam_chunk* chunks_dev, int32_t n_chunks, dou
                           double weight_decay, const float* skip_if_nonzero, sp_stream_t stream);
 int sp_loss_scale_update(float* state, float growth, float backoff, int32_t interval, sp_stream_t stream);
 
+/* Gradient clipping by GLOBAL norm with a non-finite guard for every storage mode, entirely on the device (no host sync; the reference
+ * has neither: its optimizer step is the bare torch.optim.Adam.step() of model_wrapper.py:162,190).  torch.nn.utils.clip_grad_norm_'s
+ * definition, on the chunk table the Adam step already has.  fp32 only, as sp_adam_multi.  Per optimizer step:
+ *   sp_grad_sqnorm_multi   partials[c] = sum over chunk c of (double)g[i] * (double)g[i].  One 256-thread block per chunk, float4 loads
+ *                          where g is 16-byte aligned, scalar loads otherwise.  Every product is exact in fp64 (24-bit operands: 48 bits),
+ *                          only the additions round, and their order is fixed: thread t adds its elements in index order (float4 t,
+ *                          t + 256, ... each as x, y, z, w; then the tail elements n4 * 4 + t, + 256, ...), the 64 lanes of a wave meet in
+ *                          an xor-shuffle tree (offsets 32, 16, 8, 4, 2, 1), thread 0 adds the four wave sums as ((w0 + w1) + w2) + w3.
+ *                          No atomics, nothing depends on launch order.  Reads ONLY the g and n columns of the table (p, m, v may be
+ *                          NULL); partials: n_chunks doubles, 8-byte aligned.
+ *   sp_grad_clip_finalize  one block: sum = the partials in fp64, again in a fixed order - thread t (of 256) adds partials[t],
+ *                          partials[t + 256], ... in index order, then the same wave tree and ((w0 + w1) + w2) + w3 - and
+ *                            state[0] = (float)sqrt(sum)                                  the global gradient norm
+ *                            state[1] = (float)min(1, max_norm / (sqrt(sum) + 1e-6))      the coefficient: fp64 with correctly rounded sqrt and
+ *                                                                                         divide, rounded to fp32 ONCE; 0 when sum is not finite
+ *                            state[2] = 1 if sum is not finite (an inf or a NaN among the gradients), else 0      written by every call
+ *                            state[3] += 1 when state[2] is set        steps skipped so far (only ever grows)
+ *                            state[4] += 1 when state[1] < 1 (finite)  steps clipped so far (only ever grows)
+ *                          max_norm = +inf gives exactly 1.0f (monitor and guard, never scale); max_norm <= 0 or NaN and NULL pointers
+ *                          are refused (SP_ERR_INVALID, nothing launched).
+ *   sp_adam_multi_clipped  sp_adam_multi_guarded (skip_if_nonzero as there, NULL allowed) that ALSO does nothing when clip_state[2] != 0
+ *                          and reads fp32(g * clip_state[1]) wherever that kernel reads g: the product is rounded to fp32 once and is
+ *                          never contracted into the operation that follows, so the step IS the plain step on gradients scaled by one
+ *                          fp32 multiply (Tensor.mul_), and a coefficient of exactly 1.0f is the identity.  The gradients are not
+ *                          written.  clip_state: sp_grad_clip_finalize's five floats (required). */
+int sp_grad_sqnorm_multi(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double* partials, sp_stream_t stream);
+int sp_grad_clip_finalize(const double* partials, int32_t n_partials, double max_norm, float* state, sp_stream_t stream);
+int sp_adam_multi_clipped(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double beta1, double beta2, double eps,
+                          double weight_decay, const float* skip_if_nonzero, const float* clip_state, sp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Exponential moving average (EMA) of a network's parameters, kept on the device.  The reference has NO average of its own:
  * it scores, samples and saves the raw last-iterate generator (validate() / inference() at model_wrapper.py:231-296, the checkpoint at

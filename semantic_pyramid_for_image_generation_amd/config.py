@@ -38,6 +38,9 @@ results beyond floating-point summation order.  The kernel library itself reads 
     augment               SP_AUGMENT             ""       differentiable augmentation of every image the discriminator sees, inside its ingest pass (csrc/augment.hip,
                                                           DESIGN.md 11): a comma-separated subset of color, translation, cutout; empty = off: no draw, no launch,
                                                           no allocation (the one switch here that DOES change results: it is part of the training recipe)
+    clip_grad_norm        SP_CLIP_GRAD_NORM      0        clip each network's gradients by their global norm in front of its optimizer step and skip a step whose
+                                                          norm is not finite, on the device (optim.Adam(max_grad_norm=...)); inf = monitor and guard,
+                                                          never scale; 0 / empty = off: no launch, no allocation, no logged norm (part of the training recipe too)
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -48,6 +51,17 @@ from dataclasses import dataclass
 
 def _flag(name: str, default: bool) -> bool:
     return os.environ.get(name, "1" if default else "0") == "1"
+
+
+def parse_clip_grad_norm(text) -> float:
+    """SP_CLIP_GRAD_NORM: empty, unset (None) or 0 = off (0.0); a number > 0 or "inf" = the threshold; anything else is an error."""
+    text = (text or "").strip()
+    if not text:
+        return 0.0
+    value = float(text)
+    if not value >= 0.0:                                  # negative, or NaN
+        raise ValueError("SP_CLIP_GRAD_NORM must be a number >= 0 or inf (0 = off), got %r" % text)
+    return value
 
 
 @dataclass
@@ -80,6 +94,7 @@ class Config:
     inception_weights: str = ""
     g_ema: float = 0.0
     augment: str = ""
+    clip_grad_norm: float = 0.0
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -96,7 +111,7 @@ class Config:
                    sn_skip_pack=_flag("SP_SN_SKIP_PACK", True), bn_pair=_flag("SP_BN_PAIR", True),
                    bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True),
                    inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0),
-                   augment=os.environ.get("SP_AUGMENT", ""))
+                   augment=os.environ.get("SP_AUGMENT", ""), clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")))
 
 
 CFG = Config.from_env()

@@ -14,9 +14,26 @@
 
 namespace {
 
+// g * coef rounded to fp32 ONCE (sp_adam_multi_clipped): the empty asm makes the product a value of its own, so that it cannot be
+// contracted into the g - m or g + wd * p that follows (hipcc contracts across statements, and __fmul_rn is a plain product in this
+// toolchain's headers).  g * 1.0f is g.
+__device__ __forceinline__ float mul_rounded_once(float g, float coef) {
+    float r = __fmul_rn(g, coef);
+    asm("" : "+v"(r));
+    return r;
+}
+
+// CLIP (sp_adam_multi_clipped): clip = {norm, coefficient, skip flag, ...} of sp_grad_clip_finalize - nothing is done when clip[2] != 0
+// either, and every gradient is read as fp32(g * clip[1]).  CLIP = false is the kernel sp_adam_multi / sp_adam_multi_guarded always had.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const sp_adam_chunk* __restrict__ chunks, float omb1, float beta2, float omb2,
-                                                         float eps, float wd, const float* __restrict__ skip) {
+                                                         float eps, float wd, const float* __restrict__ skip, const float* __restrict__ clip) {
     if (skip != nullptr && *skip != 0.f) return;          // sp_adam_multi_guarded: non-finite gradients were found - no update at all
+    float coef = 1.f;
+    if constexpr (CLIP) {
+        if (clip[2] != 0.f) return;                       // the sum of squares was not finite: no update at all
+        coef = clip[1];
+    }
     const sp_adam_chunk c = chunks[blockIdx.x];
     const bool vec = (((uintptr_t)c.p | (uintptr_t)c.g | (uintptr_t)c.m | (uintptr_t)c.v) & 15) == 0;
     const int n4 = vec ? c.n >> 2 : 0;
@@ -27,7 +44,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sp_adam_chunk* __
         float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w}, mm[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float g = wd != 0.f ? gg[r] + wd * pp[r] : gg[r];
+            const float gc = CLIP ? mul_rounded_once(gg[r], coef) : gg[r];
+            const float g = wd != 0.f ? gc + wd * pp[r] : gc;
             mm[r] = mm[r] + (g - mm[r]) * omb1;
             vv[r] = vv[r] * beta2 + omb2 * g * g;
             const float denom = sqrtf(vv[r]) * c.inv_sqrt_bc2 + eps;
@@ -38,7 +56,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sp_adam_chunk* __
         reinterpret_cast<float4*>(c.v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
     }
     for (int i = n4 * 4 + threadIdx.x; i < c.n; i += 256) {
-        const float g = wd != 0.f ? c.g[i] + wd * c.p[i] : c.g[i];
+        const float gc = CLIP ? mul_rounded_once(c.g[i], coef) : c.g[i];
+        const float g = wd != 0.f ? gc + wd * c.p[i] : gc;
         const float m = c.m[i] + (g - c.m[i]) * omb1;
         const float v = c.v[i] * beta2 + omb2 * g * g;
         const float denom = sqrtf(v) * c.inv_sqrt_bc2 + eps;
@@ -46,6 +65,74 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sp_adam_chunk* __
         c.m[i] = m;
         c.v[i] = v;
     }
+}
+
+// The four wave sums of a 256-thread block, added by thread 0 in the order ((w0 + w1) + w2) + w3; the result is valid in thread 0 only.
+__device__ __forceinline__ double block_sum_256_f64(double v, double* scratch /* 4 doubles, LDS */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);      // lane l holds the same tree's sum in every lane
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
+}
+
+__device__ __forceinline__ double add_squares(double acc, const float4 v) {
+    const double x = v.x, y = v.y, z = v.z, w = v.w;
+    acc += x * x;
+    acc += y * y;
+    acc += z * z;
+    acc += w * w;
+    return acc;
+}
+
+// sp_grad_sqnorm_multi: partials[chunk] = sum g[i]^2 in fp64, one block per chunk in adam_multi_kernel's form (float4 where g is 16-byte
+// aligned).  A product of two fp32 values is exact in fp64 (48 bits), so only the additions round.  Fixed order: thread t adds its
+// elements in index order (float4 i = t, t + 256, ..., each x, y, z, w; then the tail), the 64 lanes of a wave meet in an xor-shuffle
+// tree (offsets 32 ... 1), the four waves through LDS.  No atomics; only the g and n columns of the table are read.
+__global__ __launch_bounds__(256) void grad_sqnorm_multi_kernel(const sp_adam_chunk* __restrict__ chunks, double* __restrict__ partials) {
+    __shared__ double scratch[4];
+    const float* __restrict__ g = chunks[blockIdx.x].g;
+    const int n = chunks[blockIdx.x].n;
+    const int n4 = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? n >> 2 : 0;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    double acc = 0.0;
+    int i = threadIdx.x;
+    // eight loads in flight per thread (the one stream of this pass would otherwise wait for every float4 in turn); the order of the
+    // additions is the plain loop's
+    for (; i + 7 * 256 < n4; i += 8 * 256) {
+        float4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = g4[i + k * 256];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc = add_squares(acc, v[k]);
+    }
+    for (; i < n4; i += 256) acc = add_squares(acc, g4[i]);
+    for (int i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+        const double x = g[i];
+        acc += x * x;
+    }
+    const double total = block_sum_256_f64(acc, scratch);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// sp_grad_clip_finalize: one block.  sum = the partials in fp64 in a fixed order - thread t adds partials[t], partials[t + 256], ...,
+// then block_sum_256_f64's tree - and thread 0 writes the five floats of the state.
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ partials, int n, double max_norm,
+                                                                 float* __restrict__ st) {
+    __shared__ double scratch[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    const double sum = block_sum_256_f64(acc, scratch);
+    if (threadIdx.x != 0) return;
+    const bool bad = !((sum - sum) == 0.0);                            // +-inf or NaN (a sum of squares is never negative)
+    const double norm = __dsqrt_rn(sum);
+    float coef = 0.f;
+    if (!bad) coef = (float)fmin(1.0, __ddiv_rn(max_norm, norm + 1e-6));   // torch.nn.utils.clip_grad_norm_'s formula, rounded to fp32 once
+    st[0] = (float)norm;
+    st[1] = coef;
+    st[2] = bad ? 1.f : 0.f;
+    if (bad) st[3] += 1.f;
+    else if (coef < 1.f) st[4] += 1.f;
 }
 
 // Exponential moving average of a network's parameters (sp_ema_multi) and the in-place exchange that evaluates it (sp_swap_multi):
@@ -163,12 +250,41 @@ extern "C" int sp_scale_f32(float* x, int64_t numel, float factor, sp_stream_t s
     return SP_OK;
 }
 
+static int adam_multi_launch(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double beta1, double beta2, double eps, double weight_decay,
+                             const float* skip_if_nonzero, const float* clip_state, sp_stream_t stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto kernel = clip_state != nullptr ? adam_multi_kernel<true> : adam_multi_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(256), 0, s, chunks_dev, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                       (float)eps, (float)weight_decay, skip_if_nonzero, clip_state);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
 extern "C" int sp_adam_multi_guarded(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double beta1, double beta2, double eps,
                                      double weight_decay, const float* skip_if_nonzero, sp_stream_t stream) {
     SP_CHECK_ARG(chunks_dev && n_chunks > 0, "sp_adam_multi: bad args");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(n_chunks), dim3(256), 0, s, chunks_dev, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                       (float)eps, (float)weight_decay, skip_if_nonzero);
+    return adam_multi_launch(chunks_dev, n_chunks, beta1, beta2, eps, weight_decay, skip_if_nonzero, nullptr, stream);
+}
+
+extern "C" int sp_adam_multi_clipped(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double beta1, double beta2, double eps,
+                                     double weight_decay, const float* skip_if_nonzero, const float* clip_state, sp_stream_t stream) {
+    SP_CHECK_ARG(chunks_dev && n_chunks > 0 && clip_state, "sp_adam_multi_clipped: bad args (chunk table, n_chunks > 0, clip_state)");
+    return adam_multi_launch(chunks_dev, n_chunks, beta1, beta2, eps, weight_decay, skip_if_nonzero, clip_state, stream);
+}
+
+extern "C" int sp_grad_sqnorm_multi(const sp_adam_chunk* chunks_dev, int32_t n_chunks, double* partials, sp_stream_t stream) {
+    SP_CHECK_ARG(chunks_dev && n_chunks > 0 && partials && (reinterpret_cast<uintptr_t>(partials) & 7) == 0,
+                 "sp_grad_sqnorm_multi: bad args (chunk table, n_chunks > 0, 8-byte aligned partials)");
+    hipLaunchKernelGGL(grad_sqnorm_multi_kernel, dim3(n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), chunks_dev, partials);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_grad_clip_finalize(const double* partials, int32_t n_partials, double max_norm, float* state, sp_stream_t stream) {
+    SP_CHECK_ARG(partials && n_partials > 0 && state && max_norm > 0.0 && (reinterpret_cast<uintptr_t>(partials) & 7) == 0,
+                 "sp_grad_clip_finalize: bad args (partials, n_partials > 0, max_norm > 0 (inf allowed, NaN not), state)");
+    hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), partials, (int)n_partials,
+                       max_norm, state);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

@@ -19,6 +19,11 @@ beside the four reference keys of a checkpoint.  Off by default: nothing of it r
 Likewise ``augment`` (or SP_AUGMENT): differentiable augmentation - color, translation, cutout - of every image the discriminator
 sees, applied inside its ingest pass (csrc/augment.hip): three independent transforms per step from one
 (3, B, 8) draw of uniforms made in front of the latents.  Off by default: no draw, no launch, no allocation.
+And ``clip_grad_norm`` (or SP_CLIP_GRAD_NORM): each network's gradients are clipped by their global norm in front of its optimizer
+step - one norm for D's step, one for G's - and a step whose norm is not finite is skipped, in every storage mode, on the device
+(optim.Adam(max_grad_norm=...)); the two norms join the step's results and the log.  ``inf`` monitors and guards
+and never scales.  A foreign optimizer (torch.optim.Adam) gets torch.nn.utils.clip_grad_norm_ in front of its step() instead: the
+clipping and the norm, but NO guard beyond the fp16 mode's.  Off by default: no launch, no allocation, no new result.
 """
 from __future__ import annotations
 
@@ -56,7 +61,8 @@ class ModelWrapper(object):
                  gradient_reducer=None,
                  inception=None,
                  generator_ema=None,
-                 augment=None) -> None:
+                 augment=None,
+                 clip_grad_norm=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -112,6 +118,26 @@ class ModelWrapper(object):
             self.logger.hyperparameter['augment'] = ",".join(w for w, bit in ops._AUG_WORDS.items() if self._aug_policy & bit)
         self._d_params = [p for p in self.discriminator.parameters()]
         self._g_params = [p for p in self.generator.parameters()]
+        # clip_grad_norm: a threshold > 0 or inf; None: CFG.clip_grad_norm (SP_CLIP_GRAD_NORM - main.py's fixed keywords once more); 0 = off.
+        # It applies to each network on its own.  This package's Adam carries it itself (max_grad_norm: norm, coefficient, guard and step
+        # on the device); a foreign optimizer gets torch's clip_grad_norm_ in front of its step (_optimizer_step) - no guard there.
+        if clip_grad_norm is None:
+            clip_grad_norm = CFG.clip_grad_norm
+        self.clip_grad_norm = None
+        if not isinstance(clip_grad_norm, bool) and isinstance(clip_grad_norm, (int, float)) and clip_grad_norm == 0:
+            clip_grad_norm = None
+        if clip_grad_norm is not None:
+            from . import optim
+            self.clip_grad_norm = optim.check_max_grad_norm(clip_grad_norm, "clip_grad_norm")
+            for name in ('generator_optimizer', 'discriminator_optimizer'):
+                optimizer = getattr(self, name)
+                if isinstance(optimizer, optim.Adam):
+                    if optimizer.max_grad_norm is not None and optimizer.max_grad_norm != self.clip_grad_norm:
+                        raise ops.L.SempyrError("clip_grad_norm=%r, but the %s already has max_grad_norm=%r"
+                                                % (self.clip_grad_norm, name, optimizer.max_grad_norm))
+                    optimizer.max_grad_norm = self.clip_grad_norm
+            self.logger.hyperparameter['clip_grad_norm'] = str(self.clip_grad_norm)
+            self._grad_norm = {}           # "d" / "g": the norm the last optimizer step of that network measured (a device tensor)
         # every gradient of a network lives in ONE flat fp32 buffer (ops.SpectralNormBank.flat; param.grad are views of it):
         # D runs twice per backward (real, fake) and its gradients meet there instead of in 59 autograd sums, and the
         # data-parallel reducer all-reduces ranges of the buffer in place.  SP_DIRECT_GRADS=0: plain autograd gradients.
@@ -205,26 +231,51 @@ class ModelWrapper(object):
         step is skipped where one is found, and the scale is backed off / grown - all on the device for this package's Adam
         (sp_adam_multi_guarded); a foreign optimizer costs one host sync per step for the same decision.  The generator's step
         (key "g") ends with the update of its weight average where there is one (self.generator_ema): one more eager launch, skipped
-        with the step - on the device through the same flag (read before sc.update() clears it), or on the host."""
+        with the step - on the device through the same flag (read before sc.update() clears it), or on the host.
+        With clip_grad_norm this package's Adam measures the norm, clips and guards inside its step (every storage mode, no host sync),
+        and without a loss scaler the weight average follows its skip flag (with one, the scaler's flag stays: a sum of squares is
+        non-finite exactly when an element is, so the two agree).  A foreign optimizer gets torch.nn.utils.clip_grad_norm_ (foreach,
+        itself sync-free) in front of its step(): clipping and a norm, but no guard beyond the fp16 mode's.  Either way the norm of the
+        step is left in self._grad_norm[key] as a device tensor."""
+        from . import optim
         ema = self.generator_ema if key == "g" else None
         bank = self._banks.get(key)
         sc = ops.loss_scaler(bank.flat.device) if bank is not None and bank.flat is not None else None
+        own = isinstance(optimizer, optim.Adam)
+        clip = self.clip_grad_norm
+        if clip is not None and own and optimizer.max_grad_norm != clip:
+            raise ops.L.SempyrError("clip_grad_norm=%r, but the optimizer's max_grad_norm is %r" % (clip, optimizer.max_grad_norm))
+
+        if clip is not None and not own:
+            self._grad_norm[key] = torch.nn.utils.clip_grad_norm_(self._d_params if key == "d" else self._g_params, clip, foreach=True)
         if sc is None:
             optimizer.step()
             if ema is not None:
-                ema.update()
-            return
-        from . import optim
-        sc.check(bank.flat)
-        if isinstance(optimizer, optim.Adam):
-            optimizer.step(found_inf=sc.found_ptr)
-            if ema is not None:
-                ema.update(found_inf=sc.found_ptr)
-        elif not sc.values()["found"]:
-            optimizer.step()
-            if ema is not None:
-                ema.update()
-        sc.update()
+                ema.update(found_inf=ops.ptr(optimizer.skip_flag) if clip is not None and own else None)
+        else:
+            sc.check(bank.flat)
+            if own:
+                optimizer.step(found_inf=sc.found_ptr)
+                if ema is not None:
+                    ema.update(found_inf=sc.found_ptr)
+            elif not sc.values()["found"]:
+                optimizer.step()
+                if ema is not None:
+                    ema.update()
+            sc.update()
+        if clip is not None and own:
+            self._grad_norm[key] = optimizer.grad_norm
+
+    def _with_grad_norms(self, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The step's results plus, with clip_grad_norm on ONLY, the two gradient norms its optimizer steps measured (device tensors; this
+        package's Adam hands out views of its clip state, which its next step overwrites - as the graphs' static outputs are)."""
+        if self.clip_grad_norm is None:
+            return out
+        out = dict(out)
+        for key, name in (("d", "grad_norm_discriminator"), ("g", "grad_norm_generator")):
+            if key in self._grad_norm:
+                out[name] = self._grad_norm[key].detach().reshape(())
+        return out
 
     # ------------------------------------------------------------------------------------------
     def _g_pair_ok(self) -> bool:
@@ -429,9 +480,9 @@ class ModelWrapper(object):
             self._join_reduce("g")
             self._optimizer_step("g", self.generator_optimizer)
         self.iterations += 1
-        return {"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
-                "loss_generator": loss_g.detach(), "loss_generator_semantic_reconstruction": loss_rec.detach().reshape(()),
-                "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()}
+        return self._with_grad_norms({"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
+                                      "loss_generator": loss_g.detach(), "loss_generator_semantic_reconstruction": loss_rec.detach().reshape(()),
+                                      "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()})
 
     # ------------------------------------------------------------------------------------------
     def capture_graphs(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1) -> None:
@@ -617,7 +668,7 @@ class ModelWrapper(object):
             self._join_reduce("g")
             self._optimizer_step("g", self.generator_optimizer)
         self.iterations += 1
-        return st["out"]
+        return self._with_grad_norms(st["out"])
 
     # ------------------------------------------------------------------------------------------
     def _batch_signature(self, images_real, labels, masks):
@@ -729,6 +780,8 @@ class ModelWrapper(object):
         fid = self.validate()
         names = ("loss_generator_diversity", "loss_generator_semantic_reconstruction", "loss_generator",
                  "loss_discriminator_fake", "loss_discriminator_real")
+        if self.clip_grad_norm is not None:                     # the two gradient norms ride in the same host transfer
+            names += ("grad_norm_discriminator", "grad_norm_generator")
         for epoch in range(epochs):
             self.generator.train()
             self.discriminator.train()
@@ -737,7 +790,7 @@ class ModelWrapper(object):
                 self.progress_bar.update(n=images_real.shape[0])
                 out = self._train_iteration(images_real, labels, masks, w_rec, w_div, next_images_real)
                 vals = torch.stack([out[n].float().reshape(()) for n in names]).tolist()      # the single host sync
-                l_div, l_rec, l_g, l_df, l_dr = vals
+                l_div, l_rec, l_g, l_df, l_dr = vals[:5]
                 self.progress_bar.set_description(
                     'FID={:.4f}, Loss Div={:.4f}, Loss Rec={:.4f}, Loss G={:.4f}, Loss D={:.4f}'.format(
                         fid, l_div, l_rec, l_g, l_df + l_dr))
@@ -746,6 +799,8 @@ class ModelWrapper(object):
                 self.logger.log(metric_name='loss_generator', value=l_g)
                 self.logger.log(metric_name='loss_generator_semantic_reconstruction', value=l_rec)
                 self.logger.log(metric_name='loss_generator_diversity', value=l_div)
+                for n, v in zip(names[5:], vals[5:]):
+                    self.logger.log(metric_name=n, value=v)
                 self.logger.log(metric_name='iterations', value=self.progress_bar.n)
                 self.logger.log(metric_name='epoch', value=epoch)
                 if self.progress_bar.n % validate_after_n_iterations == 0:

@@ -14,6 +14,7 @@ cached plan is dropped) - round 1 incremented 286 CPU tensors and rebuilt the ta
 from __future__ import annotations
 
 import contextlib
+import ctypes
 
 import numpy as np
 import torch
@@ -31,13 +32,74 @@ class _Plan:
     __slots__ = ("key", "params", "keep", "table", "idx", "steps", "total", "synced")
 
 
+def check_max_grad_norm(value, what="max_grad_norm"):
+    """None (off), or the clipping threshold as a float: > 0, +inf allowed ("monitor and guard, never scale").  bool, NaN and values <= 0
+    are errors - 0 is not "off" here, that is spelled None."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise L.SempyrError("%s takes None or a number > 0 (inf allowed), got %r" % (what, value))
+    value = float(value)
+    if not value > 0.0:                                   # NaN fails this too
+        raise L.SempyrError("%s must be > 0 (inf allowed), got %r" % (what, value))
+    return value
+
+
 class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
+    """``max_grad_norm`` (beyond torch.optim.Adam; None = off: exactly the launches above and no state tensor): clip the gradients by
+    their GLOBAL norm over all of this optimizer's groups - torch.nn.utils.clip_grad_norm_'s definition - and skip the step when that norm
+    is not finite, all on the device.  A step is then: every group's chunk table, one sp_grad_sqnorm_multi per group into one partials
+    buffer, ONE sp_grad_clip_finalize, one sp_adam_multi_clipped per group.  The gradients are read twice and never written: the
+    step uses fp32(g * coefficient).  ``clip_state`` is the five-float device state {norm, coefficient, skip flag, steps skipped, steps
+    clipped} (include/sempyr.h: sp_grad_clip_finalize), ``grad_norm`` and ``skip_flag`` are views of its [0] and [2]; nothing is read on
+    the host.  It is no entry of ``defaults`` / ``param_groups`` / ``state_dict()``: checkpoints stay what torch.optim.Adam reads and
+    writes.  (As with ``found_inf``, the host-side step count that feeds the bias corrections still advances on a skipped step.)"""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, max_grad_norm=None, **kw):
         if amsgrad or kw.get("maximize") or kw.get("capturable") or kw.get("differentiable"):
             raise L.SempyrError("sempyr Adam supports the reference's configuration only (no amsgrad / maximize / capturable)")
+        max_grad_norm = check_max_grad_norm(max_grad_norm)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, foreach=False, fused=False)
         self._ring = {}            # per group: two pinned host tables + the event of their last upload
         self._plans = {}           # per group: cached chunk table
+        self._max_grad_norm = max_grad_norm
+        self._clip = None          # max_grad_norm only: [state (5 floats), partials (fp64, one per chunk)] on the parameters' device
+
+    # ------------------------------------------------------------------------------------------ gradient clipping
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value) -> None:
+        self._max_grad_norm = check_max_grad_norm(value)
+        if self._max_grad_norm is None:
+            self._clip = None
+
+    def _clip_buffers(self, n_partials=0):
+        """[state, partials]: allocated once on the device of the first parameter, the partials grown only when the chunk count does."""
+        if self._max_grad_norm is None:
+            raise AttributeError("this Adam has no gradient clipping state (max_grad_norm is None)")
+        if self._clip is None:
+            dev = self.param_groups[0]["params"][0].device
+            if dev.type != "cuda":
+                raise L.SempyrError("sempyr Adam needs contiguous fp32 GPU parameters (got %s)" % (dev,))
+            self._clip = [torch.zeros(5, dtype=torch.float32, device=dev), torch.zeros(max(n_partials, 1024), dtype=torch.float64, device=dev)]
+        if self._clip[1].numel() < n_partials:
+            self._clip[1] = torch.zeros(n_partials, dtype=torch.float64, device=self._clip[0].device)
+        return self._clip
+
+    @property
+    def clip_state(self) -> torch.Tensor:
+        return self._clip_buffers()[0]
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        return self._clip_buffers()[0][0]
+
+    @property
+    def skip_flag(self) -> torch.Tensor:
+        return self._clip_buffers()[0][2]
 
     # ------------------------------------------------------------------------------------------ step bookkeeping
     def _sync_steps(self) -> None:
@@ -99,57 +161,93 @@ class Adam(torch.optim.Adam):
         plan.total, plan.table, plan.idx = total, tab, idx
         return plan
 
+    def _prepare(self, gi, group):
+        """One group's share of a step in front of its launches: the cached chunk table (re)built, the step counts advanced, the two
+        bias-correction columns refreshed and the table uploaded.  Returns (plan, device table) or None where no parameter has a gradient."""
+        if group.get("amsgrad") or group.get("maximize"):
+            raise L.SempyrError("sempyr Adam: amsgrad / maximize are not supported")
+        lr, (b1, b2) = float(group["lr"]), group["betas"]
+        # the plan stays valid while every parameter keeps its gradient (and moment) storage: true for the flat gradient
+        # buffers of the training step and for captured graphs; fp32 / contiguity are checked when a plan is built
+        key = tuple((p.data_ptr(), g.data_ptr(), g.dtype == torch.float32 and g.is_contiguous())
+                    for p in group["params"] for g in (p.grad,) if g is not None)
+        plan = self._plans.get(gi)
+        if plan is None or plan.key != key:
+            if any(not k[2] for k in key):
+                raise L.SempyrError("sempyr Adam needs contiguous fp32 gradients")
+            plan = self._plans[gi] = self._build_plan(gi, group, key)
+        if plan.total == 0:
+            return None
+        plan.steps += 1.0
+        plan.synced = False
+        tab = plan.table
+        tab["step_size"] = (lr / (1.0 - b1 ** plan.steps)).astype(np.float32)[plan.idx]
+        tab["inv_sqrt_bc2"] = (1.0 / np.sqrt(1.0 - b2 ** plan.steps)).astype(np.float32)[plan.idx]
+        dev = plan.params[0].device
+        with torch.cuda.device(dev):
+            # the chunk table goes up through pinned memory (a pageable copy would make the host wait for the stream);
+            # two tables alternate and each waits for its own previous upload before it is overwritten
+            ring = self._ring.setdefault(gi, {"i": 0, "slots": [None, None]})
+            ring["i"] ^= 1
+            slot = ring["slots"][ring["i"]]
+            nbytes = tab.nbytes
+            if slot is None or slot[0].numel() < nbytes:
+                slot = [torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True), None]
+                ring["slots"][ring["i"]] = slot
+            if slot[1] is not None:
+                slot[1].synchronize()
+            slot[0][:nbytes].numpy()[:] = tab.view(np.uint8)
+            tab_dev = slot[0][:nbytes].to(dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            slot[1] = ev
+        return plan, tab_dev
+
+    @staticmethod
+    def _hyper(group):
+        (b1, b2) = group["betas"]
+        return float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])
+
     @torch.no_grad()
     def step(self, closure=None, found_inf=None):
         """found_inf (optional, the fp16 mode's ops.LossScaler): a device float; the launch updates NOTHING when it is non-zero
         (sp_adam_multi_guarded) - the step is skipped on the device, without a host sync.  (The host-side step count that feeds the
-        bias corrections still advances on a skipped step; torch's fused Adam takes it back.)"""
+        bias corrections still advances on a skipped step; torch's fused Adam takes it back.)
+
+        With ``max_grad_norm``: the tables of ALL groups first, then one sp_grad_sqnorm_multi per group, ONE sp_grad_clip_finalize over
+        all of them (the norm is global, as clip_grad_norm_ over every parameter is) and one sp_adam_multi_clipped per group, which
+        also does nothing when the norm is not finite - found_inf is passed through as before.  The same wart again: the host-side step
+        count advances on a step the device skipped."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for gi, group in enumerate(self.param_groups):
-            if group.get("amsgrad") or group.get("maximize"):
-                raise L.SempyrError("sempyr Adam: amsgrad / maximize are not supported")
-            lr, (b1, b2), eps, wd = float(group["lr"]), group["betas"], float(group["eps"]), float(group["weight_decay"])
-            # the plan stays valid while every parameter keeps its gradient (and moment) storage: true for the flat gradient
-            # buffers of the training step and for captured graphs; fp32 / contiguity are checked when a plan is built
-            key = tuple((p.data_ptr(), g.data_ptr(), g.dtype == torch.float32 and g.is_contiguous())
-                        for p in group["params"] for g in (p.grad,) if g is not None)
-            plan = self._plans.get(gi)
-            if plan is None or plan.key != key:
-                if any(not k[2] for k in key):
-                    raise L.SempyrError("sempyr Adam needs contiguous fp32 gradients")
-                plan = self._plans[gi] = self._build_plan(gi, group, key)
-            if plan.total == 0:
-                continue
-            plan.steps += 1.0
-            plan.synced = False
-            tab = plan.table
-            tab["step_size"] = (lr / (1.0 - b1 ** plan.steps)).astype(np.float32)[plan.idx]
-            tab["inv_sqrt_bc2"] = (1.0 / np.sqrt(1.0 - b2 ** plan.steps)).astype(np.float32)[plan.idx]
-            dev = plan.params[0].device
-            with torch.cuda.device(dev):
-                # the chunk table goes up through pinned memory (a pageable copy would make the host wait for the stream);
-                # two tables alternate and each waits for its own previous upload before it is overwritten
-                ring = self._ring.setdefault(gi, {"i": 0, "slots": [None, None]})
-                ring["i"] ^= 1
-                slot = ring["slots"][ring["i"]]
-                nbytes = tab.nbytes
-                if slot is None or slot[0].numel() < nbytes:
-                    slot = [torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True), None]
-                    ring["slots"][ring["i"]] = slot
-                if slot[1] is not None:
-                    slot[1].synchronize()
-                slot[0][:nbytes].numpy()[:] = tab.view(np.uint8)
-                tab_dev = slot[0][:nbytes].to(dev, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                slot[1] = ev
-                if found_inf is not None:
-                    L.call("sp_adam_multi_guarded", ptr(tab_dev), plan.total, float(b1), float(b2), eps, wd, found_inf, stream())
-                else:
-                    L.call("sp_adam_multi", ptr(tab_dev), plan.total, float(b1), float(b2), eps, wd, stream())
+        if self._max_grad_norm is None:
+            for gi, group in enumerate(self.param_groups):
+                ready = self._prepare(gi, group)
+                if ready is None:
+                    continue
+                plan, tab_dev = ready
+                with torch.cuda.device(plan.params[0].device):
+                    if found_inf is not None:
+                        L.call("sp_adam_multi_guarded", ptr(tab_dev), plan.total, *self._hyper(group), found_inf, stream())
+                    else:
+                        L.call("sp_adam_multi", ptr(tab_dev), plan.total, *self._hyper(group), stream())
+            return loss
+        ready = [(group, r) for group, r in ((group, self._prepare(gi, group)) for gi, group in enumerate(self.param_groups)) if r is not None]
+        if not ready:
+            return loss
+        state, partials = self._clip_buffers(sum(plan.total for _, (plan, _) in ready))
+        if any(plan.params[0].device != state.device for _, (plan, _) in ready):
+            raise L.SempyrError("sempyr Adam: max_grad_norm needs every parameter group on one device (the norm is global)")
+        with torch.cuda.device(state.device):
+            first = 0
+            for _, (plan, tab_dev) in ready:
+                L.call("sp_grad_sqnorm_multi", ptr(tab_dev), plan.total, ctypes.c_void_p(partials.data_ptr() + 8 * first), stream())
+                first += plan.total
+            L.call("sp_grad_clip_finalize", ptr(partials), first, self._max_grad_norm, ptr(state), stream())
+            for group, (plan, tab_dev) in ready:
+                L.call("sp_adam_multi_clipped", ptr(tab_dev), plan.total, *self._hyper(group), found_inf, ptr(state), stream())
         return loss
 
 
