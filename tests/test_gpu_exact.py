@@ -7,8 +7,11 @@ its reason in the table).  Every case is launched twice into outputs pre-filled 
 persistent; where the pitch exceeds the channel count the sentinel beyond it must survive).
 
 Left out because they cannot be exact: tanh epilogues (every route the boundary table reaches through tanh is reached here through a
-pitch that is no multiple of 8, which takes the same general epilogue), the fp8 slice (its scales), normalisation and resampling
-kernels.  Attention has its own exact tests: tests/test_gpu_attention_exact.py."""
+pitch that is no multiple of 8, which takes the same general epilogue) and the fp8 slice (its scales).  The other kernel families
+have exact tests of their own: attention in tests/test_gpu_attention_exact.py, batch norm and the bilinear x2 in
+tests/test_gpu_norm_exact.py, spectral norm and the loss-scale guards in tests/test_gpu_sn_exact.py and
+tests/test_gpu_optim_guard_exact.py, the pooling kernels in tests/test_gpu_pool_exact.py, the discriminator head and the losses in
+tests/test_gpu_loss_exact.py.  Still without: the elementwise kernels of csrc/eltwise.hip."""
 import contextlib
 import ctypes
 import functools
