@@ -494,7 +494,7 @@ int sp_ingest_image_bwd(const void* dy, int32_t cp, void* dsrc, int32_t c, int64
  *                (one fp32 multiply, then floor);  out[h, w] = e[h + t_y, w + t_x], 0 outside the frame
  *   cutout       q_y = int(H / 2 + 0.5), n_y = H + 1 - (q_y % 2), c_y = min(int(floorf(u5 * float(n_y))), n_y - 1); the rows
  *                [c_y - q_y / 2, c_y - q_y / 2 + q_y) (integer division) cut with [0, H); columns likewise from W and u6; the output
- *                is 0 inside the window.  u7 is unused.
+ *                is 0 inside the window.  u7 is unused by sp_augment_ingest / _bwd; on the gated entries below it is the gate's draw.
  * Backward, for dy on the output:
  *   g1[c, h, w] = dy[c, h - t_y, w - t_x] where that position is inside the frame and outside the window, else 0
  *   Gm = sum(g1) / (3 H W);  g2 = k g1 + (1 - k) Gm  (every input pixel);  dx_c = s g2_c + (1 - s) (g2_0 + g2_1 + g2_2) / 3
@@ -515,6 +515,39 @@ int sp_augment_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc
                       int32_t dtype, sp_stream_t stream);
 int sp_augment_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                           int32_t policy, float* partials, int32_t dtype, sp_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
+ * Adaptive augmentation (Karras et al. 2020, "ADA"): each image is transformed with a probability p that lives in DEVICE memory and
+ * is steered by an overfitting signal from the discriminator's predictions on the real images.  The reference has NO counterpart.
+ *
+ * THE GATE.  sp_augment_ingest_gated / sp_augment_ingest_bwd_gated take the arguments of sp_augment_ingest / sp_augment_ingest_bwd
+ * plus p_dev, one fp32 value in device memory, read when the kernel RUNS (a captured graph follows it without a re-capture):
+ *   image n is LIVE iff u[n * 8 + 7] < p_dev[0]   (strict, fp32; u7 is the one uniform of a row the transform itself does not read)
+ *   a live image gets exactly what the ungated entry computes for it;
+ *   a dead image gets BIT FOR BIT what sp_ingest_image / sp_ingest_image_bwd write for it with scale3 / shift3 NULL, in every storage
+ *   type: no color arithmetic ((b - m) * 1 + m is not the identity in fp32), no translation, no window.
+ * p_dev[0] = 1.0f therefore equals the ungated entries bit for bit and p_dev[0] = 0.0f is the plain ingest.  The statistics launches
+ * skip a dead image's blocks: its partials are never written and never read, and `partials` still needs no initialisation.  Fixed-order
+ * partial sums, no float atomics, as the ungated entries (the same kernels).  A NULL p_dev is refused (SP_ERR_INVALID, nothing launched).
+ *
+ * THE CONTROLLER.  Two one-block launches on ONE state buffer of 8 x 4 bytes in device memory (4-byte aligned):
+ *   slot 0 f32 p   1 f32 r_last   2 i32 pos   3 i32 neg   4 i32 total   5 i32 steps   6 i32 adjustments   7 reserved, zero
+ *   sp_ada_observe  pos += #(pred[i] > threshold), neg += #(pred[i] < threshold), total += numel.  Equal values and NaN count in total
+ *                   only.  Integer arithmetic: the result does not depend on any order.  numel in [1, 2^24], else refused.
+ *   sp_ada_adjust   steps += 1.  If steps >= interval: steps = 0, and if total > 0 also
+ *                     r = float(pos - neg) / float(total)        both conversions round to nearest; ONE fp32 division
+ *                     p = fminf(1, fmaxf(0, p + d)),  d = step if r > target, -step if r < target, else 0        ONE fp32 addition
+ *                     r_last = r;  pos = neg = total = 0;  adjustments += 1
+ *                   (a full window with total == 0 only starts the step count again).  interval >= 1, step in [0, 1], target in
+ *                   [-1, 1], else refused (NaN included).  A refusal launches nothing and leaves the state as it is.
+ * &state[0] is what the gated entries take as p_dev.
+ * ---------------------------------------------------------------------------------------------- */
+int sp_augment_ingest_gated(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                            int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
+                            const float* p_dev, int32_t dtype, sp_stream_t stream);
+int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                                int32_t policy, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream);
+int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream);
+int sp_ada_adjust(void* state, int32_t interval, float target, float step, sp_stream_t stream);
 int sp_mask_concat(const void* feat, const float* mask, void* out, int64_t pixels, int32_t c, int32_t cp,
                    int32_t dtype, sp_stream_t stream);
 int sp_mask_mul_2d(const void* feat, int32_t ldf, const float* mask, void* out, int32_t ldo, int32_t batch,

@@ -38,6 +38,9 @@ results beyond floating-point summation order.  The kernel library itself reads 
     augment               SP_AUGMENT             ""       differentiable augmentation of every image the discriminator sees, inside its ingest pass (csrc/augment.hip,
                                                           DESIGN.md 11): a comma-separated subset of color, translation, cutout; empty = off: no draw, no launch,
                                                           no allocation (the one switch here that DOES change results: it is part of the training recipe)
+    augment_p             SP_AUGMENT_P           ""       with augment only: the probability with which each image is transformed (csrc/augment.hip: the gate,
+                                                          DESIGN.md 15) - a number in [0, 1] = fixed; "adaptive" or "adaptive:<target>" = steered on the device from
+                                                          D's predictions on the real images (ops.AdaptiveAugment); empty = off: every image, no launch, no allocation
     clip_grad_norm        SP_CLIP_GRAD_NORM      0        clip each network's gradients by their global norm in front of its optimizer step and skip a step whose
                                                           norm is not finite, on the device (optim.Adam(max_grad_norm=...)); inf = monitor and guard,
                                                           never scale; 0 / empty = off: no launch, no allocation, no logged norm (part of the training recipe too)
@@ -94,6 +97,7 @@ class Config:
     inception_weights: str = ""
     g_ema: float = 0.0
     augment: str = ""
+    augment_p: str = ""
     clip_grad_norm: float = 0.0
 
     @classmethod
@@ -111,7 +115,8 @@ class Config:
                    sn_skip_pack=_flag("SP_SN_SKIP_PACK", True), bn_pair=_flag("SP_BN_PAIR", True),
                    bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True),
                    inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0),
-                   augment=os.environ.get("SP_AUGMENT", ""), clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")))
+                   augment=os.environ.get("SP_AUGMENT", ""), augment_p=os.environ.get("SP_AUGMENT_P", "").strip(),
+                   clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")))
 
 
 CFG = Config.from_env()

@@ -12,6 +12,7 @@
 //                out[h, w] = e[h + t_y, w + t_x], 0 outside the frame
 //   cutout       q_y = int(H / 2 + 0.5), n_y = H + 1 - (q_y % 2), c_y = min(int(floorf(u5 * float(n_y))), n_y - 1); rows
 //                [c_y - q_y / 2, c_y - q_y / 2 + q_y) cut with [0, H) are zeroed, columns likewise from W and u6; u7 is unused
+//                by the ungated entries and is the GATE's draw on the gated ones (below)
 // Backward:  g1[c, h, w] = dy[c, h - t_y, w - t_x] where that position is inside the frame and outside the window, else 0;
 //            Gm = sum(g1) / (3 H W);  g2 = k g1 + (1 - k) Gm;  dx_c = s g2_c + (1 - s) (g2_0 + g2_1 + g2_2) / 3.
 //
@@ -19,6 +20,16 @@
 // shuffle + LDS block sum, ONE fp32 partial per block - and the apply launch - grid (blocks, images), which adds its image's
 // partials in slice order (no float atomics: bit-identical from run to run).  Without color: the apply launch alone, which then only
 // moves data.  u is read and decoded on the device, so a captured graph replays with whatever the buffer holds.
+//
+// THE GATE (Karras et al. 2020, "ADA").  sp_augment_ingest_gated / sp_augment_ingest_bwd_gated take p_dev, one fp32
+// value in device memory read when the kernel RUNS: image n is LIVE iff u[n * 8 + 7] < p_dev[0] (strict, fp32).  A live image gets what the
+// ungated entry computes for it; a dead one gets bit for bit what sp_ingest_image / sp_ingest_image_bwd write with scale3 / shift3 NULL -
+// no color arithmetic, no translation, no window ((b - m) * 1 + m is not the identity in fp32).  The same kernels serve both forms: the
+// ungated entries pass p_dev = NULL (every image live), so p = 1 IS the ungated result and p = 0 the plain ingest.  A dead image's
+// statistics blocks leave at once and write nothing; its apply blocks never read its partials.
+// THE CONTROLLER.  sp_ada_observe counts D's predictions on the real images above and below a threshold into the 8-word state,
+// sp_ada_adjust moves p by one step per full window from r = (pos - neg) / total; both are one block, integer counts (no order
+// dependence), state read and written on the device - a captured graph holds the observe launch and follows p through the pointer.
 #include "common.h"
 
 namespace {
@@ -76,14 +87,35 @@ __device__ __forceinline__ float aug_total(const float* __restrict__ partials, i
 
 template <typename T> struct Vec16 { static constexpr int N = 16 / (int)sizeof(T); };
 
+// the gate: true where image n is transformed.  p_dev == NULL: the ungated entries (every image).  Strict fp32 compare; a NaN p is dead.
+__device__ __forceinline__ bool aug_gate(const float* __restrict__ u, const float* __restrict__ p_dev, int n) {
+    return p_dev == nullptr || u[(long)n * 8 + 7] < p_dev[0];
+}
+
+// one padded NHWC pixel: 3 values and CP - 3 zeros (one 16-byte store where the pitch is 16 bytes)
+template <typename TD>
+__device__ __forceinline__ void aug_st_padded(TD* __restrict__ d, int CP, const float (&e)[3]) {
+    if (CP == 4) {
+        const float v[4] = {e[0], e[1], e[2], 0.f};
+        VecIO<TD, 4>::st(d, v);
+    } else if (sizeof(TD) == 2 && CP == 8) {
+        const float v[8] = {e[0], e[1], e[2], 0.f, 0.f, 0.f, 0.f, 0.f};
+        VecIO<bf16, 8>::st(reinterpret_cast<bf16*>(d), v);
+    } else {
+        for (int c = 0; c < CP; ++c) Elem<TD>::st(d + c, c < 3 ? e[c] : 0.f);
+    }
+}
+
 // ---- statistics, forward: partial sums of the raw source --------------------------------------------
 // dense: the image's 3 H W elements are one contiguous, 16-byte aligned run (NCHW-contiguous or channels-last): 16-byte loads.
 template <typename TS>
 __global__ __launch_bounds__(256) void aug_stats_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw, int H, int W,
-                                                            int dense, float* __restrict__ partials) {
+                                                            int dense, float* __restrict__ partials, const float* __restrict__ u,
+                                                            const float* __restrict__ p_dev) {
     __shared__ float red[4];
     constexpr int V = Vec16<TS>::N;
     const int n = blockIdx.y;
+    if (!aug_gate(u, p_dev, n)) return;      // a dead image: nobody reads its partials (block-uniform)
     const long total = 3L * H * W;
     const long beg = (long)blockIdx.x * AUG_FWD_SLICE;
     const long end = beg + AUG_FWD_SLICE < total ? beg + AUG_FWD_SLICE : total;
@@ -115,10 +147,23 @@ __global__ __launch_bounds__(256) void aug_stats_fwd_kernel(const TS* __restrict
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw,
                                                             TD* __restrict__ dst, AugGeom g, int CP, const float* __restrict__ u,
-                                                            int policy, const float* __restrict__ partials, int nsl) {
+                                                            int policy, const float* __restrict__ partials, int nsl,
+                                                            const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
-    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const int HW = g.H * g.W;
+    if (!aug_gate(u, p_dev, n)) {
+        // a dead image: ingest_kernel's values (x * 1 + 0 with scale3 / shift3 NULL: x, and -0 becomes +0) through this kernel's stores
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+            const int h = p / g.W, w = p - h * g.W;
+            const TS* s = src + (long)n * sn + (long)h * sh + (long)w * sw;
+            float e[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc) + 0.f;
+            aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
+        }
+        return;
+    }
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const bool color = (policy & SP_AUG_COLOR) != 0;
     float M = 0.f;
     if (color) M = aug_total(partials, n, nsl) / (float)(3 * HW) + a.o;
@@ -141,16 +186,7 @@ __global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict
                 }
             }
         }
-        TD* d = dst + ((long)n * HW + p) * CP;
-        if (CP == 4) {
-            const float v[4] = {e[0], e[1], e[2], 0.f};
-            VecIO<TD, 4>::st(d, v);
-        } else if (sizeof(TD) == 2 && CP == 8) {
-            const float v[8] = {e[0], e[1], e[2], 0.f, 0.f, 0.f, 0.f, 0.f};
-            VecIO<bf16, 8>::st(reinterpret_cast<bf16*>(d), v);
-        } else {
-            for (int c = 0; c < CP; ++c) Elem<TD>::st(d + c, c < 3 ? e[c] : 0.f);
-        }
+        aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
     }
 }
 
@@ -171,9 +207,10 @@ __device__ __forceinline__ void aug_ld3(const T* __restrict__ p, int CP, float (
 // ---- statistics, backward: partial sums of g1 = the dy values that reach an input pixel --------------
 template <typename T>
 __global__ __launch_bounds__(256) void aug_stats_bwd_kernel(const T* __restrict__ dy, int CP, AugGeom g, const float* __restrict__ u,
-                                                            int policy, float* __restrict__ partials) {
+                                                            int policy, float* __restrict__ partials, const float* __restrict__ p_dev) {
     __shared__ float red[4];
     const int n = blockIdx.y;
+    if (!aug_gate(u, p_dev, n)) return;      // a dead image: nobody reads its partials (block-uniform)
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const int HW = g.H * g.W;
     const int beg = blockIdx.x * AUG_BWD_SLICE;
@@ -195,10 +232,21 @@ __global__ __launch_bounds__(256) void aug_stats_bwd_kernel(const T* __restrict_
 template <typename T>
 __global__ __launch_bounds__(256) void aug_apply_bwd_kernel(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, AugGeom g,
                                                             const float* __restrict__ u, int policy, const float* __restrict__ partials,
-                                                            int nsl) {
+                                                            int nsl, const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
-    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const int HW = g.H * g.W;
+    if (!aug_gate(u, p_dev, n)) {
+        // a dead image: ingest_bwd_kernel's values (dy * 1 with scale3 NULL), element by element as it stores them
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+            float v[3];
+            aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
+            T* d = dsrc + ((long)n * HW + p) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+        }
+        return;
+    }
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const bool color = (policy & SP_AUG_COLOR) != 0;
     float Gm = 0.f;
     if (color) Gm = aug_total(partials, n, nsl) / (float)(3 * HW);
@@ -234,27 +282,120 @@ inline bool aug_dims_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h 
 
 template <typename TS, typename TD>
 void aug_launch_fwd(const void* src, long sn, long sc, long sh, long sw, void* dst, int n, const AugGeom& g, int cp, const float* u,
-                    int policy, float* partials, hipStream_t s) {
+                    int policy, float* partials, const float* p_dev, hipStream_t s) {
     int nsl = 0;
     if (policy & SP_AUG_COLOR) {
         nsl = aug_slices(g.H, g.W, false);
         const bool run = (sw == 1 && sh == g.W && sc == (long)g.H * g.W) || (sc == 1 && sw == 3 && sh == 3L * g.W);
         const int dense = run && reinterpret_cast<uintptr_t>(src) % 16 == 0 && (sn * (long)sizeof(TS)) % 16 == 0;
-        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw, g.H, g.W, dense, partials);
+        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw, g.H, g.W, dense, partials, u, p_dev);
     }
     hipLaunchKernelGGL((aug_apply_fwd_kernel<TS, TD>), dim3(aug_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw,
-                       (TD*)dst, g, cp, u, policy, partials, nsl);
+                       (TD*)dst, g, cp, u, policy, partials, nsl, p_dev);
 }
 
 template <typename T>
-void aug_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g, const float* u, int policy, float* partials, hipStream_t s) {
+void aug_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g, const float* u, int policy, float* partials,
+                    const float* p_dev, hipStream_t s) {
     int nsl = 0;
     if (policy & SP_AUG_COLOR) {
         nsl = aug_slices(g.H, g.W, true);
-        hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, n), dim3(256), 0, s, (const T*)dy, cp, g, u, policy, partials);
+        hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, n), dim3(256), 0, s, (const T*)dy, cp, g, u, policy, partials, p_dev);
     }
     hipLaunchKernelGGL(aug_apply_bwd_kernel<T>, dim3(aug_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const T*)dy, cp, (T*)dsrc, g, u, policy,
-                       partials, nsl);
+                       partials, nsl, p_dev);
+}
+
+// ---- the gate's controller: 8 words of state {p, r_last, pos, neg, total, steps, adjustments, reserved} ----------------------
+// ONE block of 1024 threads: integer counts, so the result does not depend on any order.  Eight independent 16-byte loads per thread
+// and trip where pred is 16-byte aligned (a single dependent load per trip took 15 us for D's 51 200 predictions); a slot past the end
+// holds the threshold itself, which counts on neither side.
+__global__ __launch_bounds__(1024) void ada_observe_kernel(const float* __restrict__ pred, int numel, float threshold, int* __restrict__ state) {
+    __shared__ int cnt[2][16];
+    constexpr int U = 8;
+    int pos = 0, neg = 0;
+    const int n4 = (reinterpret_cast<uintptr_t>(pred) & 15) == 0 ? numel / 4 : 0;
+    const float4* p4 = reinterpret_cast<const float4*>(pred);
+    for (int base = 0; base < n4; base += U * 1024) {
+        float4 v[U];
+#pragma unroll
+        for (int r = 0; r < U; ++r) {
+            const int i = base + r * 1024 + (int)threadIdx.x;
+            v[r] = i < n4 ? p4[i] : make_float4(threshold, threshold, threshold, threshold);
+        }
+#pragma unroll
+        for (int r = 0; r < U; ++r) {
+            pos += (v[r].x > threshold) + (v[r].y > threshold) + (v[r].z > threshold) + (v[r].w > threshold);
+            neg += (v[r].x < threshold) + (v[r].y < threshold) + (v[r].z < threshold) + (v[r].w < threshold);
+        }
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < numel; i += 1024) {
+        const float x = pred[i];
+        pos += x > threshold ? 1 : 0;      // equal values and NaN: neither
+        neg += x < threshold ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { pos += __shfl_xor(pos, o, 64); neg += __shfl_xor(neg, o, 64); }
+    if ((threadIdx.x & 63) == 0) { cnt[0][threadIdx.x >> 6] = pos; cnt[1][threadIdx.x >> 6] = neg; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tp = 0, tn = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { tp += cnt[0][k]; tn += cnt[1][k]; }
+        state[2] += tp;
+        state[3] += tn;
+        state[4] += numel;
+    }
+}
+
+__global__ void ada_adjust_kernel(int* __restrict__ state, int interval, float target, float step) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float* f = reinterpret_cast<float*>(state);
+    const int steps = state[5] + 1;
+    if (steps < interval) { state[5] = steps; return; }
+    state[5] = 0;
+    const int total = state[4];
+    if (total <= 0) return;                // a full window without an observation: only the step count starts again
+    const float r = __fdiv_rn(__int2float_rn(state[2] - state[3]), __int2float_rn(total));
+    const float d = r > target ? step : (r < target ? -step : 0.f);
+    f[0] = fminf(1.f, fmaxf(0.f, __fadd_rn(f[0], d)));
+    f[1] = r;
+    state[2] = 0; state[3] = 0; state[4] = 0;
+    state[6] += 1;
+}
+
+// the bodies of the ungated and gated entry points (p_dev == NULL: ungated)
+int aug_ingest(const char* name, const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst, int32_t n,
+               int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials, const float* p_dev, int32_t dtype,
+               sp_stream_t stream) {
+    SP_CHECK_ARG(src && dst && u && cp >= 3, "%s: bad args", name);
+    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "%s: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", name, n, h, w_);
+    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "%s: bad dtype", name);
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "%s: bad policy %d", name, policy);
+    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "%s: the color policy needs the partials buffer", name);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const AugGeom g = aug_geom(h, w_);
+    if (src_dtype == SP_F32 && dtype == SP_F32) aug_launch_fwd<float, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
+    else if (src_dtype == SP_F32 && dtype == SP_BF16) aug_launch_fwd<float, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
+    else if (src_dtype == SP_BF16 && dtype == SP_BF16) aug_launch_fwd<bf16, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
+    else aug_launch_fwd<bf16, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+int aug_ingest_bwd(const char* name, const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u, int32_t policy,
+                   float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(dy && dsrc && u && cp >= 3, "%s: bad args", name);
+    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "%s: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", name, n, h, w_);
+    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "%s: bad dtype", name);
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "%s: bad policy %d", name, policy);
+    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "%s: the color policy needs the partials buffer", name);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const AugGeom g = aug_geom(h, w_);
+    if (dtype == SP_F32) aug_launch_bwd<float>(dy, cp, dsrc, n, g, u, policy, partials, p_dev, s);
+    else aug_launch_bwd<bf16>(dy, cp, dsrc, n, g, u, policy, partials, p_dev, s);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
 }
 
 }  // namespace
@@ -268,32 +409,40 @@ extern "C" int sp_augment_slices(int32_t h, int32_t w_, int32_t backward, int64_
 extern "C" int sp_augment_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                  int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
                                  int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(src && dst && u && cp >= 3, "sp_augment_ingest: bad args");
-    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_ingest: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
-    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "sp_augment_ingest: bad dtype");
-    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_ingest: bad policy %d", policy);
-    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_ingest: the color policy needs the partials buffer");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const AugGeom g = aug_geom(h, w_);
-    if (src_dtype == SP_F32 && dtype == SP_F32) aug_launch_fwd<float, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
-    else if (src_dtype == SP_F32 && dtype == SP_BF16) aug_launch_fwd<float, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
-    else if (src_dtype == SP_BF16 && dtype == SP_BF16) aug_launch_fwd<bf16, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
-    else aug_launch_fwd<bf16, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, s);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    return aug_ingest("sp_augment_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, partials, nullptr, dtype, stream);
 }
 
 extern "C" int sp_augment_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                      int32_t policy, float* partials, int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(dy && dsrc && u && cp >= 3, "sp_augment_ingest_bwd: bad args");
-    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_ingest_bwd: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
-    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_augment_ingest_bwd: bad dtype");
-    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_ingest_bwd: bad policy %d", policy);
-    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_ingest_bwd: the color policy needs the partials buffer");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const AugGeom g = aug_geom(h, w_);
-    if (dtype == SP_F32) aug_launch_bwd<float>(dy, cp, dsrc, n, g, u, policy, partials, s);
-    else aug_launch_bwd<bf16>(dy, cp, dsrc, n, g, u, policy, partials, s);
+    return aug_ingest_bwd("sp_augment_ingest_bwd", dy, cp, dsrc, n, h, w_, u, policy, partials, nullptr, dtype, stream);
+}
+
+extern "C" int sp_augment_ingest_gated(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                                       int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
+                                       const float* p_dev, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(p_dev, "sp_augment_ingest_gated: p_dev is NULL (the ungated entry is sp_augment_ingest)");
+    return aug_ingest("sp_augment_ingest_gated", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, partials, p_dev, dtype, stream);
+}
+
+extern "C" int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                                           int32_t policy, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(p_dev, "sp_augment_ingest_bwd_gated: p_dev is NULL (the ungated entry is sp_augment_ingest_bwd)");
+    return aug_ingest_bwd("sp_augment_ingest_bwd_gated", dy, cp, dsrc, n, h, w_, u, policy, partials, p_dev, dtype, stream);
+}
+
+extern "C" int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream) {
+    SP_CHECK_ARG(pred && state, "sp_ada_observe: bad args");
+    SP_CHECK_ARG(numel >= 1 && numel <= (1L << 24), "sp_ada_observe: numel=%ld (need 1 ... 2^24)", (long)numel);
+    hipLaunchKernelGGL(ada_observe_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pred, (int)numel, threshold, (int*)state);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_ada_adjust(void* state, int32_t interval, float target, float step, sp_stream_t stream) {
+    SP_CHECK_ARG(state && interval >= 1, "sp_ada_adjust: bad args (interval=%d)", interval);
+    SP_CHECK_ARG(step >= 0.f && step <= 1.f && target >= -1.f && target <= 1.f, "sp_ada_adjust: step=%g target=%g (need step in [0, 1], target in [-1, 1])",
+                 (double)step, (double)target);
+    hipLaunchKernelGGL(ada_adjust_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), (int*)state, interval, target, step);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

@@ -24,6 +24,10 @@ step - one norm for D's step, one for G's - and a step whose norm is not finite 
 (optim.Adam(max_grad_norm=...)); the two norms join the step's results and the log.  ``inf`` monitors and guards
 and never scales.  A foreign optimizer (torch.optim.Adam) gets torch.nn.utils.clip_grad_norm_ in front of its step() instead: the
 clipping and the norm, but NO guard beyond the fp16 mode's.  Off by default: no launch, no allocation, no new result.
+And ``augment_p`` (or SP_AUGMENT_P; with ``augment`` only): each image in front of D is transformed with probability p and passes
+untouched otherwise (the gate of csrc/augment.hip) - a fixed p, or one steered on the device from D's predictions
+on the real images (ops.AdaptiveAugment: one counting launch inside the D phase, one adjusting launch behind Adam(G), no host sync);
+p and the signal r_t then join the step's results, the log and the checkpoint.  Off by default: every image is transformed, as above.
 """
 from __future__ import annotations
 
@@ -62,7 +66,8 @@ class ModelWrapper(object):
                  inception=None,
                  generator_ema=None,
                  augment=None,
-                 clip_grad_norm=None) -> None:
+                 clip_grad_norm=None,
+                 augment_p=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -116,6 +121,10 @@ class ModelWrapper(object):
                 raise ops.L.SempyrError("augment: the transform runs inside this package's Discriminator's ingest pass; a caller's own "
                                         "discriminator module cannot be armed")
             self.logger.hyperparameter['augment'] = ",".join(w for w, bit in ops._AUG_WORDS.items() if self._aug_policy & bit)
+        # augment_p: the probability with which an image in front of D is transformed (with augment only).  None: CFG.augment_p
+        # (SP_AUGMENT_P); "" = off: every image, nothing below exists.  A number in [0, 1]: fixed.  "adaptive" / "adaptive:<target>" or an
+        # ops.AdaptiveAugment: steered on the device.  _ada owns the device state; it is allocated HERE, outside any graph's pool.
+        self._ada = self._make_augment_p(CFG.augment_p if augment_p is None else augment_p)
         self._d_params = [p for p in self.discriminator.parameters()]
         self._g_params = [p for p in self.generator.parameters()]
         # clip_grad_norm: a threshold > 0 or inf; None: CFG.clip_grad_norm (SP_CLIP_GRAD_NORM - main.py's fixed keywords once more); 0 = off.
@@ -266,6 +275,44 @@ class ModelWrapper(object):
         if clip is not None and own:
             self._grad_norm[key] = optimizer.grad_norm
 
+    def _make_augment_p(self, spec):
+        """The constructor's augment_p -> an ops.AdaptiveAugment (fixed or adaptive) or None (off)."""
+        if isinstance(spec, str):
+            spec = spec.strip()
+            if spec == "":
+                return None
+        if isinstance(spec, bool) or spec is None:
+            raise ops.L.SempyrError("augment_p takes a probability in [0, 1], 'adaptive', 'adaptive:<target>' or an ops.AdaptiveAugment (got %r)" % (spec,))
+        if not self._aug_policy:
+            raise ops.L.SempyrError("augment_p=%r, but this ModelWrapper augments nothing (augment / SP_AUGMENT): there is nothing to gate" % (spec,))
+        device = next(self.discriminator.parameters()).device
+        if isinstance(spec, ops.AdaptiveAugment):
+            ada = spec
+        else:
+            if device.type != "cuda":
+                raise ops.L.SempyrError("augment_p: the gate's state lives on the discriminator's GPU; move the discriminator there first")
+            try:
+                if isinstance(spec, str) and (spec == "adaptive" or spec.startswith("adaptive:")):
+                    ada = ops.AdaptiveAugment(device, target=float(spec[9:])) if spec != "adaptive" else ops.AdaptiveAugment(device)
+                else:
+                    ada = ops.AdaptiveAugment(device, p=float(spec), adaptive=False)
+            except ValueError:
+                raise ops.L.SempyrError("augment_p takes a probability in [0, 1], 'adaptive' or 'adaptive:<target>' (got %r)" % (spec,)) from None
+        self.logger.hyperparameter['augment_p'] = str(dict(ada.settings(), p=float(ada.p)) if not ada.adaptive else ada.settings())
+        return ada
+
+    def _adaptive(self) -> bool:
+        return self._ada is not None and self._ada.adaptive
+
+    def _with_augment_p(self, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The step's results plus, with the adaptive controller on ONLY, p and the signal r_t of the last full window: views of the
+        controller's device state (as the gradient norms are views of the clip state), read after the step's adjust launch."""
+        if not self._adaptive():
+            return out
+        out = dict(out)
+        out["augment_p"], out["augment_rt"] = self._ada.p.reshape(()), self._ada.r.reshape(())
+        return out
+
     def _with_grad_norms(self, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """The step's results plus, with clip_grad_norm on ONLY, the two gradient norms its optimizer steps measured (device tensors; this
         package's Adam hands out views of its clip state, which its next step overwrites - as the graphs' static outputs are)."""
@@ -303,10 +350,12 @@ class ModelWrapper(object):
             return fn(*args)
         D = self.discriminator
         D._augment = (self._aug_policy,) + tuple(rows)
+        D._augment_p = self._ada.p if self._ada is not None else None
         try:
             return fn(*args)
         finally:
             D._augment = None
+            D._augment_p = None
 
     def _d_phase(self, images_real, labels, labels_f, masks, noise_d, features_real=None, noise_g=None, aug_u=None):
         """model_wrapper.py:136-160: forward passes and backward of the discriminator step (everything but Adam).  features_real: the
@@ -338,6 +387,10 @@ class ModelWrapper(object):
         else:
             prediction_real = self._d_call(D, None if aug_u is None else (aug_u[0],), images_real, labels)
             prediction_fake = self._d_call(D, None if aug_u is None else (aug_u[1],), images_fake, labels)
+        if self._adaptive():
+            # the overfitting signal's counts (sp_ada_observe): one launch on D's fp32 predictions, inside the first captured graph; p
+            # itself moves only behind Adam(G) (train_step), so every gate of this step reads the same value
+            self._ada.observe(prediction_real)
         loss_d_real, loss_d_fake = self.discriminator_loss(prediction_real, prediction_fake)
         self._arm_reducer("d")
         # d(real + fake): one seed per loss instead of a sum kernel and autograd's own seed (model_wrapper.py:158-160)
@@ -479,10 +532,12 @@ class ModelWrapper(object):
         with profiling.range("Adam(G)"):
             self._join_reduce("g")
             self._optimizer_step("g", self.generator_optimizer)
+            if self._adaptive():
+                self._ada.adjust(images_real.shape[0])
         self.iterations += 1
-        return self._with_grad_norms({"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
+        return self._with_augment_p(self._with_grad_norms({"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
                                       "loss_generator": loss_g.detach(), "loss_generator_semantic_reconstruction": loss_rec.detach().reshape(()),
-                                      "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()})
+                                      "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()}))
 
     # ------------------------------------------------------------------------------------------
     def capture_graphs(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1) -> None:
@@ -667,8 +722,10 @@ class ModelWrapper(object):
         with profiling.range("Adam(G)"):
             self._join_reduce("g")
             self._optimizer_step("g", self.generator_optimizer)
+            if self._adaptive():
+                self._ada.adjust(st["images"].shape[0])             # eager, as the optimizer steps: p moves between replays
         self.iterations += 1
-        return self._with_grad_norms(st["out"])
+        return self._with_augment_p(self._with_grad_norms(st["out"]))
 
     # ------------------------------------------------------------------------------------------
     def _batch_signature(self, images_real, labels, masks):
@@ -782,6 +839,8 @@ class ModelWrapper(object):
                  "loss_discriminator_fake", "loss_discriminator_real")
         if self.clip_grad_norm is not None:                     # the two gradient norms ride in the same host transfer
             names += ("grad_norm_discriminator", "grad_norm_generator")
+        if self._adaptive():                                    # ... and so do the gate's probability and its signal
+            names += ("augment_p", "augment_rt")
         for epoch in range(epochs):
             self.generator.train()
             self.discriminator.train()
@@ -821,6 +880,8 @@ class ModelWrapper(object):
                     # beyond the four reference keys: a state dict a Generator loads as it is (averaged parameters, live buffers)
                     checkpoint["generator_ema"] = ema.averaged_state_dict(self.generator)
                     checkpoint["generator_ema_state"] = {"decay": ema.decay, "warmup": ema.warmup, "num_updates": ema.num_updates}
+                if self._adaptive():
+                    checkpoint["augment_state"] = self._ada.state_dict()
                 torch.save(checkpoint,
                            os.path.join(self.path_save_models, 'checkpoint_{}.pt'.format(str(epoch).zfill(3))))
             self.inference(device=device)
@@ -840,6 +901,18 @@ class ModelWrapper(object):
                 raise ops.L.SempyrError("load_generator_ema(): neither a ParameterEMA state nor a checkpoint with a 'generator_ema' key")
             state = dict(state.get("generator_ema_state", {}), parameters=state["generator_ema"])
         ema.load_state_dict(state)
+
+    def load_augment_state(self, checkpoint_or_state) -> None:
+        """Restores the adaptive augmentation's controller for a resumed run: a checkpoint of train() (its "augment_state" key) or an
+        AdaptiveAugment.state_dict().  The device state is written in place: captured graphs stay valid."""
+        if not self._adaptive():
+            raise ops.L.SempyrError("load_augment_state(): this ModelWrapper steers no augmentation probability (augment_p / SP_AUGMENT_P)")
+        state = checkpoint_or_state
+        if "state" not in state:
+            if "augment_state" not in state:
+                raise ops.L.SempyrError("load_augment_state(): neither an AdaptiveAugment state nor a checkpoint with an 'augment_state' key")
+            state = state["augment_state"]
+        self._ada.load_state_dict(state)
 
     def _ema_scope(self, use_ema):
         """The context validate() / inference() run in: the generator's weight average swapped in (ParameterEMA.applied) where one

@@ -753,7 +753,9 @@ class Discriminator(nn.Module):
         self._bank = ops.SpectralNormBank(_collect_sn(self), _non_sn_params(self))
         # Differentiable augmentation (csrc/augment.hip; beyond the reference): ModelWrapper arms ONE call by setting this to
         # (policy mask, u) for forward or (policy mask, u_a, u_b) for forward_pair and clears it behind the call.  None: the plain ingest.
+        # _augment_p rides with it: None, or the gate's probability (a 1-element fp32 device tensor, ops.AdaptiveAugment.p) of that call.
         self._augment = None
+        self._augment_p = None
 
     def _ingest(self, input: torch.Tensor, dt) -> torch.Tensor:
         aug = getattr(self, "_augment", None)
@@ -761,7 +763,7 @@ class Discriminator(nn.Module):
             return ops.ingest_image(input, dt)
         if len(aug) != 2:
             raise ops.L.SempyrError("Discriminator.forward: armed for forward_pair (two rows of uniforms)")
-        return ops.augment_ingest_image(input, dt, aug[1], aug[0])
+        return ops.augment_ingest_image(input, dt, aug[1], aug[0], p=getattr(self, "_augment_p", None))
 
     def forward(self, input: torch.Tensor, class_id: torch.Tensor) -> torch.Tensor:
         dt = ops.compute_dtype()
@@ -825,7 +827,7 @@ class Discriminator(nn.Module):
             if aug is None:
                 x = ops.ingest_image_pair(input_a, input_b, dt)
             else:
-                x = ops.augment_ingest_image_pair(input_a, input_b, dt, aug[1], aug[2], aug[0])
+                x = ops.augment_ingest_image_pair(input_a, input_b, dt, aug[1], aug[2], aug[0], p=getattr(self, "_augment_p", None))
             x = L[0](x)
             x = L[3](L[2](L[1](x)))
             x = L[7](L[6](L[5](L[4](x))))

@@ -1822,10 +1822,25 @@ def _augment_partials(n, h, w, policy, backward, device):
     return torch.empty((n, augment_slices(h, w, backward)), dtype=torch.float32, device=device)
 
 
-def _augment_fwd(img, y_ptr, dtype, cp, u, policy):
+def _augment_gate(p, device):
+    """The gate's probability for the gated entries (include/sempyr.h): a 1-element fp32 tensor on the images' device, read by the
+    kernel when it runs.  None: the ungated entries."""
+    if p is None:
+        return None
+    if not (isinstance(p, torch.Tensor) and p.is_cuda and p.device == device and p.dtype == torch.float32 and p.numel() == 1):
+        raise L.SempyrError("the gated augmenting ingest takes p as a 1-element fp32 tensor on the images' GPU (got %r)"
+                            % (((tuple(p.shape), p.dtype, str(p.device)) if isinstance(p, torch.Tensor) else p),))
+    return p
+
+
+def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None):
     n, _, h, w = img.shape
     sn, scs, sh, sw = img.stride()
     part = _augment_partials(n, h, w, policy, False, img.device)
+    if p is not None:
+        L.call("sp_augment_ingest_gated", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(part),
+               ptr(p), sp_dtype(dtype), stream())
+        return
     L.call("sp_augment_ingest", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(part),
            sp_dtype(dtype), stream())
 
@@ -1834,13 +1849,14 @@ class _AugmentIngestFn(torch.autograd.Function):
     """_IngestFn with the augmentation applied in the same pass: T(img; u) -> NHWC with zero-padded channels; gradients flow through T."""
 
     @staticmethod
-    def forward(ctx, img, dtype, u, policy):
+    def forward(ctx, img, dtype, u, policy, p=None):
         n, c, h, w = img.shape
         cp = pad_channels(c, dtype)
         y = nhwc_empty(n, cp, h, w, dtype, img.device)
-        _augment_fwd(img, ptr(y), dtype, cp, u, policy)
+        _augment_fwd(img, ptr(y), dtype, cp, u, policy, p)
         ctx.cfg = (n, h, w, cp, policy, img.dtype)
         ctx.u = u
+        ctx.p = p                          # the gate reads the SAME device value in the backward pass: p is constant through a step
         return y
 
     @staticmethod
@@ -1849,26 +1865,34 @@ class _AugmentIngestFn(torch.autograd.Function):
         dy = as_nhwc(dy)
         dsrc = nhwc_empty(n, 3, h, w, dy.dtype, dy.device)
         part = _augment_partials(n, h, w, policy, True, dy.device)
-        L.call("sp_augment_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), sp_dtype(dy.dtype), stream())
+        if ctx.p is not None:
+            L.call("sp_augment_ingest_bwd_gated", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), ptr(ctx.p),
+                   sp_dtype(dy.dtype), stream())
+        else:
+            L.call("sp_augment_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), sp_dtype(dy.dtype), stream())
         if dsrc.dtype != src_dtype:
             dsrc = dsrc.to(src_dtype)
-        return dsrc, None, None, None
+        return dsrc, None, None, None, None
 
 
-def augment_ingest_image(img: torch.Tensor, dtype, u: torch.Tensor, policy) -> torch.Tensor:
+def augment_ingest_image(img: torch.Tensor, dtype, u: torch.Tensor, policy, p: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ingest_image(T(img; u), dtype) in the ingest's own pass (csrc/augment.hip): u = (n, 8) fp32 uniforms on the device, one row per
-    image, decoded in the kernel (augment_decode restates it); policy = "color,translation,cutout", a subset, or the bit mask."""
+    image, decoded in the kernel (augment_decode restates it); policy = "color,translation,cutout", a subset, or the bit mask.
+    p: None, or the gate - a 1-element fp32 device tensor read when the kernels run: image i is transformed iff u[i, 7] < p, else it
+    is ingested as ingest_image does it, bit for bit, forward and backward (AdaptiveAugment.p is such a tensor)."""
     policy = _augment_args(img, u, policy)
-    return _AugmentIngestFn.apply(img, dtype, u, policy)
+    return _AugmentIngestFn.apply(img, dtype, u, policy, _augment_gate(p, img.device))
 
 
-def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u_a: torch.Tensor, u_b: torch.Tensor, policy) -> torch.Tensor:
+def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u_a: torch.Tensor, u_b: torch.Tensor, policy,
+                              p: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ingest_image_pair with each batch under its own transform: ONE padded NHWC batch [T(a; u_a) | T(b; u_b)], no autograd of
-    its own (the discriminator step needs no image gradient)."""
+    its own (the discriminator step needs no image gradient).  p: the gate of augment_ingest_image, for both batches."""
     with torch.no_grad():
         img_a, img_b = img_a.detach(), img_b.detach()
         policy = _augment_args(img_a, u_a, policy)
         _augment_args(img_b, u_b, policy)
+        p = _augment_gate(p, img_a.device)
         na, c, h, w = img_a.shape
         if tuple(img_b.shape[1:]) != (c, h, w):
             raise L.SempyrError("augment_ingest_image_pair: image shapes differ (%s, %s)" % (tuple(img_a.shape), tuple(img_b.shape)))
@@ -1876,8 +1900,89 @@ def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u
         y = nhwc_empty(na + img_b.shape[0], cp, h, w, dtype, img_a.device)
         esz = y.element_size()
         for img, u, off in ((img_a, u_a, 0), (img_b, u_b, na)):
-            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy)
+            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy, p)
     return y
+
+
+class AdaptiveAugment:
+    """The probability p with which the augmenting ingest transforms an image, and its controller (Karras et al. 2020, "ADA";
+    include/sempyr.h: sp_ada_observe / sp_ada_adjust).  The state - {p, r_last, pos, neg, total, steps,
+    adjustments, reserved}, 8 x 4 bytes - lives on the device from construction on (never inside a graph's pool); the gated ingest
+    kernels read p through a pointer when they run and the two controller launches read and write the rest, so nothing syncs with the
+    host and a captured graph follows p without a re-capture (as ops.LossScaler's scale).
+        observe(pred)   counts pred > threshold / pred < threshold (D's fp32 predictions on the real images; threshold 0.5 is the midpoint
+                        of the LSGAN targets 1 and 0)
+        adjust(batch)   once per training step: after `interval` steps r = (pos - neg) / total, and p moves by
+                        step = float32(interval * batch / speed_images) towards 1 while r > target, towards 0 while r < target
+    adaptive=False: a fixed p that is never observed or adjusted (both calls do nothing)."""
+
+    def __init__(self, device, p: float = 0.0, target: float = 0.6, interval: int = 4, speed_images: int = 500_000, threshold: float = 0.5,
+                 adaptive: bool = True):
+        p, target, threshold = float(p), float(target), float(threshold)
+        if not 0.0 <= p <= 1.0:
+            raise L.SempyrError("AdaptiveAugment: p must lie in [0, 1], got %r" % (p,))
+        if not -1.0 <= target <= 1.0:
+            raise L.SempyrError("AdaptiveAugment: target must lie in [-1, 1], got %r" % (target,))
+        if int(interval) != interval or interval < 1:
+            raise L.SempyrError("AdaptiveAugment: interval must be an integer >= 1, got %r" % (interval,))
+        if not speed_images > 0:
+            raise L.SempyrError("AdaptiveAugment: speed_images must be > 0, got %r" % (speed_images,))
+        if threshold != threshold:
+            raise L.SempyrError("AdaptiveAugment: threshold is NaN")
+        self.target, self.interval, self.speed_images, self.threshold, self.adaptive = target, int(interval), speed_images, threshold, bool(adaptive)
+        self.state = torch.zeros(8, dtype=torch.int32, device=device)
+        self.state[0:1].view(torch.float32).fill_(p)
+
+    @property
+    def p(self) -> torch.Tensor:
+        """The 1-element fp32 view of the state that the gated ingest takes."""
+        return self.state[0:1].view(torch.float32)
+
+    @property
+    def r(self) -> torch.Tensor:
+        return self.state[1:2].view(torch.float32)
+
+    def step_size(self, batch: int) -> float:
+        """float32(interval * batch / speed_images), at most 1."""
+        return min(1.0, float(torch.tensor(self.interval * int(batch) / self.speed_images, dtype=torch.float32)))
+
+    def observe(self, pred: torch.Tensor) -> None:
+        if not self.adaptive:
+            return
+        pred = pred.detach()
+        if not (pred.is_cuda and pred.device == self.state.device and pred.dtype == torch.float32 and pred.numel() >= 1):
+            raise L.SempyrError("AdaptiveAugment.observe: fp32 predictions on the state's GPU (got %s %s)" % (tuple(pred.shape), pred.dtype))
+        pred = pred.contiguous()
+        L.call("sp_ada_observe", ptr(pred), pred.numel(), self.threshold, ptr(self.state), stream())
+
+    def adjust(self, batch: int) -> None:
+        if not self.adaptive:
+            return
+        L.call("sp_ada_adjust", ptr(self.state), self.interval, self.target, self.step_size(batch), stream())
+
+    def values(self) -> dict:
+        """Host copy (syncs): for tests and logs."""
+        s = self.state.cpu()
+        f = s[0:2].view(torch.float32).tolist()
+        i = s.tolist()
+        return {"p": f[0], "r_last": f[1], "pos": i[2], "neg": i[3], "total": i[4], "steps": i[5], "adjustments": i[6]}
+
+    def settings(self) -> dict:
+        return {"target": self.target, "interval": self.interval, "speed_images": self.speed_images, "threshold": self.threshold,
+                "adaptive": self.adaptive}
+
+    def state_dict(self) -> dict:
+        return dict(self.settings(), state=self.state.detach().cpu().clone())
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restores the device state IN PLACE (captured graphs have its address baked in) and the settings that came with it."""
+        state = sd["state"]
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == (8,)):
+            raise L.SempyrError("AdaptiveAugment.load_state_dict: 'state' must be an int32 tensor of 8 words")
+        for key in ("target", "interval", "speed_images", "threshold", "adaptive"):
+            if key in sd:
+                setattr(self, key, sd[key])
+        self.state.copy_(state)
 
 
 def mask_concat(feat: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
