@@ -548,6 +548,63 @@ int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsrc, int32_t 
                                 int32_t policy, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream);
 int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream);
 int sp_ada_adjust(void* state, int32_t interval, float target, float step, sp_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
+ * Geometric augmentation inside the ingest pass (Karras et al. 2020, "ADA": pixel blitting and general geometric transforms): x-flip,
+ * 90-degree rotations, isotropic scaling and arbitrary rotation compose with the translation above into ONE 2 x 3 affine map per image,
+ * applied by bilinear resampling; the backward pass is the exact adjoint computed by GATHER (no float atomics, fixed summation order).
+ * The reference has NO counterpart.  DESIGN.md section 16.
+ *
+ * One application takes the image's row u of 8 uniforms, with the meaning above (u0-u2 color, u3-u4 translation, u5-u6 cutout, u7 the
+ * gate), a row v of 4 fp32 uniforms in [0, 1) and `geom`, any OR of SP_GEOM_*; a part that is left out is the identity and is not computed.
+ * Decode (fp32):
+ *   flip  = v0 < 0.5f
+ *   k     = min(int(floorf(4 * v1)), 3)
+ *   e     = 0.8f * v2 - 0.4f, g = exp2f(-e): the image is magnified by 2^e, in [0.758, 1.32)
+ *   theta = (v3 - 0.5f) * float(pi / 2), c = cosf(theta), s = sinf(theta): [-45, 45) degrees, so with rot90 the whole circle is reached
+ *   t_y, t_x from u3, u4 as above (0 without SP_AUG_TRANSLATION);  cy = (H - 1) / 2, cx = (W - 1) / 2
+ * The INVERSE map takes an output pixel (h, w) to source coordinates (y, x).  Its linear part, rows in (y, x) order, is
+ *   L = F . Q^k . g . [[c, -s], [s, c]],   Q = [[0, 1], [-1, 0]] applied as exact row swaps and sign changes,   F = diag(1, -1) if flip
+ * and the full map is (y, x) = L . ((h, w) + (t_y, t_x) - (cy, cx)) + (cy, cx).  The table row of an image is
+ *   {m00, m01, m02, m10, m11, m12, 0, 0},   (m00 m01; m10 m11) = L,   (m02, m12) = L . (t_y - cy, t_x - cx) + (cy, cx)
+ * evaluated as m02 = (m00 (t_y - cy) + m01 (t_x - cx)) + cy with every product and sum rounded once.  A row without scale and rotate is
+ * EXACT: entries in {-1, 0, 1}, exact offsets.  SP_GEOM_ROT90 needs H == W.
+ * Forward, with e the color transform above of the SOURCE (pointwise, evaluated at each tap; its mean is still one reduction of the
+ * raw input):
+ *   y = (m00 h + m01 w) + m02, x = (m10 h + m11 w) + m12   every product and sum rounded once to fp32 (no fused multiply-add), so that
+ *   y0 = floorf(y), fy = y - y0; x0, fx likewise            both passes see the same coordinates
+ *   out[c, h, w] = (1 - fy) ((1 - fx) e[y0, x0] + fx e[y0, x0 + 1]) + fy ((1 - fx) e[y0 + 1, x0] + fx e[y0 + 1, x0 + 1])
+ *   a tap outside the frame contributes 0 (zero padding: grid_sample(bilinear, zeros, align_corners=True) on the same coordinates);
+ *   then the cutout window, in OUTPUT coordinates, zeroes its pixels.
+ * Backward:  g1[c, i, j] = sum over output pixels (h, w) outside the window of omega(h, w -> i, j) dy[c, h, w], omega the bilinear weight
+ * above; then the color backward unchanged (Gm = sum(g1) / (3 H W), g2, dx).  For source pixel (i, j) the contributing outputs lie
+ * within |h - round(q_y)| <= 2, |w - round(q_x)| <= 2 of q = L^-1 ((i, j) - (m02, m12)): at most 25 candidates, each one's (y, x)
+ * recomputed with the forward's expression, accumulated in row-major order; the candidate ranges are clipped to the frame BEFORE the
+ * loops, so no index depends on the table's values.  sum(g1) is taken over OUTPUT pixels outside the window as
+ * sum (dy_0 + dy_1 + dy_2) (sum of the in-frame tap weights), partials in a fixed order.
+ * The apply entries are specified for the tables the decode writes and for any table whose linear part's inverse A = L^-1 has
+ * |a00| + |a01| <= 2 and |a10| + |a11| <= 2 (the pre-image of a tap square then has half-extent <= 2 per axis, and rounding adds 0.5).
+ * Any other table (a singular one, NaN) is still safe - every index is checked against the frame - but the backward may miss
+ * contributions.
+ *
+ * sp_augment_geom_decode      ONE tiny launch: n x 8 floats into `table` from u (n x 8) and v (n x 4); reads only `policy`'s
+ *                             translation bit.  geom in 1 ... 15, else refused.
+ * sp_augment_geom_ingest      stands where sp_augment_ingest_gated stands; sp_augment_geom_ingest_bwd where sp_augment_ingest_bwd_gated
+ *                             stands.  `policy` contributes its color and cutout bits only: the translation is in the table.  p_dev is
+ *                             the gate (image n is live iff u[n * 8 + 7] < p_dev[0]; a dead image gets bit for bit what
+ *                             sp_ingest_image(_bwd) writes); p_dev == NULL: every image is live.
+ * sp_augment_geom_slices      host-only: sizes `partials` (n x slices floats, needed with SP_AUG_COLOR only).
+ * Refusals launch nothing: NULL pointers, cp < 3, a bad dtype, a bad geom, rot90 on a non-square map, missing partials with color.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SP_GEOM_XFLIP = 1, SP_GEOM_ROT90 = 2, SP_GEOM_SCALE = 4, SP_GEOM_ROTATE = 8 };
+int sp_augment_geom_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out);
+int sp_augment_geom_decode(const float* u, const float* v, int32_t n, int32_t h, int32_t w_, int32_t policy, int32_t geom,
+                           float* table, sp_stream_t stream);
+int sp_augment_geom_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                           int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, const float* table,
+                           float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream);
+int sp_augment_geom_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                               int32_t policy, const float* table, float* partials, const float* p_dev, int32_t dtype,
+                               sp_stream_t stream);
 int sp_mask_concat(const void* feat, const float* mask, void* out, int64_t pixels, int32_t c, int32_t cp,
                    int32_t dtype, sp_stream_t stream);
 int sp_mask_mul_2d(const void* feat, int32_t ldf, const float* mask, void* out, int32_t ldo, int32_t batch,

@@ -30,6 +30,35 @@
 // THE CONTROLLER.  sp_ada_observe counts D's predictions on the real images above and below a threshold into the 8-word state,
 // sp_ada_adjust moves p by one step per full window from r = (pos - neg) / total; both are one block, integer counts (no order
 // dependence), state read and written on the device - a captured graph holds the observe launch and follows p through the pointer.
+//
+// THE GEOMETRIC FAMILY (Karras et al. 2020: pixel blitting and general geometric transforms; include/sempyr.h
+// repeats it).  x-flip, 90-degree rotations, isotropic scaling and arbitrary rotation compose with the translation into ONE 2 x 3 affine
+// map per image.  A row v of 4 fp32 uniforms in [0, 1) joins u; geom = any OR of SP_GEOM_XFLIP 1 / ROT90 2 / SCALE 4 / ROTATE 8, a
+// part left out is the identity and is not computed.  Decode (fp32):
+//   flip = v0 < 0.5f;  k = min(int(floorf(4 v1)), 3);  e = 0.8f v2 - 0.4f, g = exp2f(-e) (magnification 2^e in [0.758, 1.32));
+//   theta = (v3 - 0.5f) float(pi / 2), c = cosf(theta), s = sinf(theta) ([-45, 45) degrees: with rot90 the whole circle);
+//   t_y, t_x from u3, u4 as above (0 without SP_AUG_TRANSLATION);  cy = (H - 1) / 2, cx = (W - 1) / 2.
+// The INVERSE map takes an output pixel (h, w) to source coordinates (y, x) = L ((h, w) + (t_y, t_x) - (cy, cx)) + (cy, cx) with
+//   L = F Q^k g [[c, -s], [s, c]], rows in (y, x) order, Q = [[0, 1], [-1, 0]] as exact row swaps and sign changes, F = diag(1, -1) if flip.
+// Table row: {m00, m01, m02, m10, m11, m12, 0, 0}, (m00 m01; m10 m11) = L, (m02, m12) = L (t_y - cy, t_x - cx) + (cy, cx); a row
+// without scale and rotate is EXACT (entries in {-1, 0, 1}).  rot90 needs H == W.
+// Forward: y = (m00 h + m01 w) + m02, x likewise - products and sums rounded once each, never fused (geom_coord), so both passes get the
+// same bits; y0 = floorf(y), fy = y - y0;  out = (1 - fy) ((1 - fx) e[y0, x0] + fx e[y0, x0 + 1]) + fy ((1 - fx) e[y0 + 1, x0] + fx
+// e[y0 + 1, x0 + 1]) with e the color transform of the SOURCE evaluated at each tap (its mean M is still the one reduction of the raw
+// input); a tap outside the frame contributes 0 (grid_sample bilinear / zeros / align_corners=True); then the cutout window zeroes its
+// OUTPUT pixels.  Backward: g1[c, i, j] = sum over outputs (h, w) outside the window of omega(h, w -> i, j) dy[c, h, w], then the color
+// backward unchanged.  It is a GATHER: for source pixel (i, j), q = L^-1 ((i, j) - (m02, m12)), and the contributing outputs lie within
+// |h - round(q_y)| <= 2, |w - round(q_x)| <= 2 - the pre-image of the tap square (-1, 1)^2 under L^-1 = A has half-extent |a00| + |a01|
+// <= 1.32 sqrt(2) = 1.87 per axis and rounding adds 0.5, so 2.37 < 3.  At most 25 candidates, each one's (y, x) recomputed by the
+// forward's expression, summed in row-major order, the ranges cut with the frame BEFORE the loops: no index depends on the table's
+// values (the forward compares floorf(y) with the frame as a float before it becomes an int).  The apply entries are specified for the
+// tables the decode writes and for any table with |a00| + |a01| <= 2 and |a10| + |a11| <= 2, A the inverse of its linear part; any
+// other table is safe but its backward may miss contributions.  sum(g1) for the color backward is taken over OUTPUT pixels outside the
+// window, (dy_0 + dy_1 + dy_2) x (sum of the in-frame tap weights), partials in slice order as above.  The gate is unchanged.
+// LAUNCHES: decode - one thread per image, n x 8 floats; apply forward - grid (blocks, images), one output pixel per thread in 16 x 16
+// tiles (geom_tile_pixel), four taps x three channels from the strided source (a block's footprint is a patch of some 30 x 30 pixels
+// that stays in L2; no LDS staging), one 16-byte padded store; backward - one source pixel per thread in the same tiles, up to 25
+// 16-byte loads of padded dy pixels, L^-1 once per block.
 #include "common.h"
 
 namespace {
@@ -306,6 +335,297 @@ void aug_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g,
                        partials, nsl, p_dev);
 }
 
+// ---- the geometric family: one 2 x 3 affine map per image, bilinear taps (header comment: THE GEOMETRIC FAMILY) ----------------------
+struct GeomMap { float m00, m01, m02, m10, m11, m12; };
+
+__device__ __forceinline__ GeomMap geom_map(const float* __restrict__ table, int n) {
+    const float* t = table + (long)n * 8;
+    GeomMap m;
+    m.m00 = t[0]; m.m01 = t[1]; m.m02 = t[2]; m.m10 = t[3]; m.m11 = t[4]; m.m12 = t[5];
+    return m;
+}
+
+// (m0 h + m1 w) + m2 with every product and sum rounded once: no contraction, so the forward and the backward kernel (and the decode's
+// offsets, which use the same form) get the SAME bits from the same operands
+__device__ __forceinline__ float geom_coord(float m0, float m1, float m2, float h, float w) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(m0, h), __fmul_rn(m1, w)), m2);
+}
+
+// one axis of a bilinear sample at coordinate y: taps i0 and i0 + 1 with weights w0 = 1 - f and w1 = f; in0 / in1: that tap is inside
+// [0, size).  y0 is compared as a float BEFORE it becomes an int: a coordinate far outside the frame (or NaN) never becomes an index.
+struct GeomAxis { int i0; float w0, w1; bool in0, in1; };
+
+__device__ __forceinline__ GeomAxis geom_axis(float y, int size) {
+    GeomAxis a;
+    const float y0 = floorf(y);
+    const float f = __fsub_rn(y, y0);
+    const bool near = y0 >= -1.f && y0 <= (float)(size - 1);
+    a.i0 = near ? (int)y0 : -2;
+    a.w0 = __fsub_rn(1.f, f);
+    a.w1 = f;
+    a.in0 = near && a.i0 >= 0;
+    a.in1 = near && a.i0 + 1 < size;
+    return a;
+}
+
+// The apply kernels walk the map in tiles of 16 x 16 pixels, one per block and trip, each wave an 8 x 8 quarter: under a rotation a
+// wave's taps then fall into ~11 source rows (8 at 0 degrees, the same after a rot90) where 64 pixels of one output row would fall
+// into up to 64.  false: the pixel lies outside the map (a partial tile).
+__device__ __forceinline__ bool geom_tile_pixel(int t, int tiles_w, const AugGeom& g, int& h, int& w) {
+    const int th = t / tiles_w, q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    h = th * 16 + (q >> 1) * 8 + (lane >> 3);
+    w = (t - th * tiles_w) * 16 + (q & 1) * 8 + (lane & 7);
+    return h < g.H && w < g.W;
+}
+
+__device__ __forceinline__ bool aug_in_window(const AugImage& a, int h, int w) { return h >= a.y0 && h < a.y1 && w >= a.x0 && w < a.x1; }
+
+// decode: one thread per image, n x 8 floats.  Without scale and rotate the linear part is never multiplied: entries in {-1, 0, 1}.
+__global__ __launch_bounds__(64) void geom_decode_kernel(const float* __restrict__ u, const float* __restrict__ v, int n, AugGeom g, int policy,
+                                                         int geom, float* __restrict__ table) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float* vi = v + (long)i * 4;
+    float a00 = 1.f, a01 = 0.f, a10 = 0.f, a11 = 1.f;
+    if (geom & (SP_GEOM_SCALE | SP_GEOM_ROTATE)) {
+        float gs = 1.f, c = 1.f, s = 0.f;
+        if (geom & SP_GEOM_SCALE) gs = exp2f(-__fsub_rn(__fmul_rn(0.8f, vi[2]), 0.4f));
+        if (geom & SP_GEOM_ROTATE) {
+            const float theta = __fmul_rn(__fsub_rn(vi[3], 0.5f), 1.57079632679489661923f);
+            c = cosf(theta);
+            s = sinf(theta);
+        }
+        a00 = __fmul_rn(gs, c); a01 = -__fmul_rn(gs, s); a10 = __fmul_rn(gs, s); a11 = __fmul_rn(gs, c);
+    }
+    if (geom & SP_GEOM_ROT90) {
+        const int k = min((int)floorf(__fmul_rn(4.f, vi[1])), 3);
+        for (int r = 0; r < k; ++r) {          // Q . A: the rows swap, the new second row changes sign
+            const float b0 = a00, b1 = a01;
+            a00 = a10; a01 = a11; a10 = -b0; a11 = -b1;
+        }
+    }
+    if ((geom & SP_GEOM_XFLIP) && vi[0] < 0.5f) { a10 = -a10; a11 = -a11; }
+    const AugImage t = aug_decode(u + (long)i * 8, policy & SP_AUG_TRANSLATION, g);
+    const float cy = (float)(g.H - 1) * 0.5f, cx = (float)(g.W - 1) * 0.5f;
+    const float dy = (float)t.ty - cy, dx = (float)t.tx - cx;          // half-integers: exact
+    float* row = table + (long)i * 8;
+    row[0] = a00; row[1] = a01; row[2] = geom_coord(a00, a01, cy, dy, dx);
+    row[3] = a10; row[4] = a11; row[5] = geom_coord(a10, a11, cx, dy, dx);
+    row[6] = 0.f; row[7] = 0.f;
+}
+
+// color of one source pixel (aug_apply_fwd_kernel's expressions)
+__device__ __forceinline__ void geom_color(float (&e)[3], const AugImage& a, float M) {
+    float b[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] = e[c] + a.o;
+    const float m = (b[0] + b[1] + b[2]) / 3.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float sat = (b[c] - m) * a.s + m;
+        e[c] = (sat - M) * a.k + M;
+    }
+}
+
+// ---- apply, forward: one output pixel per thread, four taps x three channels from the strided source, color per tap -------------------
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw,
+                                                             TD* __restrict__ dst, AugGeom g, int CP, const float* __restrict__ u,
+                                                             int policy, const float* __restrict__ table,
+                                                             const float* __restrict__ partials, int nsl, const float* __restrict__ p_dev) {
+    const int n = blockIdx.y;
+    const int HW = g.H * g.W;
+    const TS* base = src + (long)n * sn;
+    if (!aug_gate(u, p_dev, n)) {
+        // a dead image: aug_apply_fwd_kernel's dead path, value for value
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+            const int h = p / g.W, w = p - h * g.W;
+            const TS* s = base + (long)h * sh + (long)w * sw;
+            float e[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc) + 0.f;
+            aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
+        }
+        return;
+    }
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);          // color and cutout only: the entry masks the translation out
+    const GeomMap m = geom_map(table, n);
+    const bool color = (policy & SP_AUG_COLOR) != 0;
+    float M = 0.f;
+    if (color) M = aug_total(partials, n, nsl) / (float)(3 * HW) + a.o;
+    const int tiles_w = (g.W + 15) >> 4, tiles = ((g.H + 15) >> 4) * tiles_w;
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        int h, w;
+        if (!geom_tile_pixel(t, tiles_w, g, h, w)) continue;
+        const int p = h * g.W + w;
+        float e[3] = {0.f, 0.f, 0.f};
+        if (!aug_in_window(a, h, w)) {
+            const float hf = (float)h, wf = (float)w;
+            const GeomAxis ay = geom_axis(geom_coord(m.m00, m.m01, m.m02, hf, wf), g.H);
+            const GeomAxis ax = geom_axis(geom_coord(m.m10, m.m11, m.m12, hf, wf), g.W);
+            float t[2][2][3];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    t[r][q][0] = t[r][q][1] = t[r][q][2] = 0.f;
+                    if ((r ? ay.in1 : ay.in0) && (q ? ax.in1 : ax.in0)) {          // a tap outside the frame contributes 0
+                        const TS* s = base + (long)(ay.i0 + r) * sh + (long)(ax.i0 + q) * sw;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) t[r][q][c] = Elem<TS>::ld(s + c * sc);
+                        if (color) geom_color(t[r][q], a, M);
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                e[c] = ay.w0 * (ax.w0 * t[0][0][c] + ax.w1 * t[0][1][c]) + ay.w1 * (ax.w0 * t[1][0][c] + ax.w1 * t[1][1][c]);
+        }
+        aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
+    }
+}
+
+// ---- statistics, backward: sum(g1) taken over OUTPUT pixels: (dy_0 + dy_1 + dy_2) x (sum of the in-frame tap weights) ----------------
+template <typename T>
+__global__ __launch_bounds__(256) void geom_stats_bwd_kernel(const T* __restrict__ dy, int CP, AugGeom g, const float* __restrict__ u,
+                                                             int policy, const float* __restrict__ table, float* __restrict__ partials,
+                                                             const float* __restrict__ p_dev) {
+    __shared__ float red[4];
+    const int n = blockIdx.y;
+    if (!aug_gate(u, p_dev, n)) return;      // a dead image: nobody reads its partials (block-uniform)
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
+    const GeomMap m = geom_map(table, n);
+    const int HW = g.H * g.W;
+    const int beg = blockIdx.x * AUG_BWD_SLICE;
+    const int end = beg + AUG_BWD_SLICE < HW ? beg + AUG_BWD_SLICE : HW;
+    float acc = 0.f;
+    for (int p = beg + threadIdx.x; p < end; p += 256) {
+        const int h = p / g.W, w = p - h * g.W;
+        if (aug_in_window(a, h, w)) continue;
+        const float hf = (float)h, wf = (float)w;
+        const GeomAxis ay = geom_axis(geom_coord(m.m00, m.m01, m.m02, hf, wf), g.H);
+        const GeomAxis ax = geom_axis(geom_coord(m.m10, m.m11, m.m12, hf, wf), g.W);
+        if ((ay.in0 || ay.in1) && (ax.in0 || ax.in1)) {
+            const float wy = (ay.in0 ? ay.w0 : 0.f) + (ay.in1 ? ay.w1 : 0.f);
+            const float wx = (ax.in0 ? ax.w0 : 0.f) + (ax.in1 ? ax.w1 : 0.f);
+            float v[3];
+            aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
+            acc += ((v[0] + v[1]) + v[2]) * (wy * wx);
+        }
+    }
+    acc = block_sum_256(acc, red);
+    if (threadIdx.x == 0) partials[(long)n * gridDim.x + blockIdx.x] = acc;
+}
+
+// ---- apply, backward: the adjoint by GATHER.  One source pixel per thread; the outputs that can reach it lie within 2 of
+// round(L^-1 ((i, j) - (m02, m12))) on each axis (header comment: the box), at most 25 padded dy pixels, row-major order ---------------
+template <typename T>
+__global__ __launch_bounds__(256) void geom_apply_bwd_kernel(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, AugGeom g,
+                                                             const float* __restrict__ u, int policy, const float* __restrict__ table,
+                                                             const float* __restrict__ partials, int nsl, const float* __restrict__ p_dev) {
+    __shared__ float inv[4];
+    const int n = blockIdx.y;
+    const int HW = g.H * g.W;
+    if (!aug_gate(u, p_dev, n)) {            // (block-uniform: no thread of a dead image's block reaches the barrier below)
+        // a dead image: aug_apply_bwd_kernel's dead path, value for value
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+            float v[3];
+            aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
+            T* d = dsrc + ((long)n * HW + p) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+        }
+        return;
+    }
+    const AugImage a = aug_decode(u + (long)n * 8, policy, g);
+    const GeomMap m = geom_map(table, n);
+    if (threadIdx.x == 0) {                  // the image's L^-1, once per block
+        const float r = 1.f / (m.m00 * m.m11 - m.m01 * m.m10);
+        inv[0] = m.m11 * r; inv[1] = -m.m01 * r; inv[2] = -m.m10 * r; inv[3] = m.m00 * r;
+    }
+    __syncthreads();
+    const bool color = (policy & SP_AUG_COLOR) != 0;
+    float Gm = 0.f;
+    if (color) Gm = aug_total(partials, n, nsl) / (float)(3 * HW);
+    const int tiles_w = (g.W + 15) >> 4, tiles = ((g.H + 15) >> 4) * tiles_w;
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        int i, j;
+        if (!geom_tile_pixel(t, tiles_w, g, i, j)) continue;
+        const int p = i * g.W + j;
+        const float fi = (float)i, fj = (float)j;
+        const float di = fi - m.m02, dj = fj - m.m12;
+        // the box's centre, clipped as a FLOAT (fmaxf / fminf drop a NaN), then the ranges cut with the frame: from here on no index
+        // depends on the table's values
+        const int hc = (int)fminf(fmaxf(rintf(inv[0] * di + inv[1] * dj), -3.f), (float)(g.H + 2));
+        const int wc = (int)fminf(fmaxf(rintf(inv[2] * di + inv[3] * dj), -3.f), (float)(g.W + 2));
+        const int h_lo = max(hc - 2, 0), h_hi = min(hc + 2, g.H - 1);
+        const int w_lo = max(wc - 2, 0), w_hi = min(wc + 2, g.W - 1);
+        float v[3] = {0.f, 0.f, 0.f};
+        for (int h = h_lo; h <= h_hi; ++h) {
+            for (int w = w_lo; w <= w_hi; ++w) {
+                if (aug_in_window(a, h, w)) continue;
+                const float hf = (float)h, wf = (float)w;
+                const float y = geom_coord(m.m00, m.m01, m.m02, hf, wf);          // the forward's expression: the forward's weights
+                const float y0 = floorf(y);
+                const bool r0 = y0 == fi, r1 = y0 + 1.f == fi;
+                if (!(r0 || r1)) continue;
+                const float x = geom_coord(m.m10, m.m11, m.m12, hf, wf);
+                const float x0 = floorf(x);
+                const bool q0 = x0 == fj, q1 = x0 + 1.f == fj;
+                if (!(q0 || q1)) continue;
+                const float fy = __fsub_rn(y, y0), fx = __fsub_rn(x, x0);
+                const float wgt = (r0 ? __fsub_rn(1.f, fy) : fy) * (q0 ? __fsub_rn(1.f, fx) : fx);
+                float d[3];
+                aug_ld3(dy + ((long)n * HW + (long)h * g.W + w) * CP, CP, d);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] += wgt * d[c];
+            }
+        }
+        if (color) {
+            float g2[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g2[c] = a.k * v[c] + (1.f - a.k) * Gm;
+            const float mm = (g2[0] + g2[1] + g2[2]) / 3.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = a.s * g2[c] + (1.f - a.s) * mm;
+        }
+        T* d = dsrc + ((long)n * HW + p) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+    }
+}
+
+inline int geom_apply_blocks(int h, int w) {          // one block per 16 x 16 tile, AUG_APPLY_BLOCKS at most (the kernels stride beyond)
+    const int b = ((h + 15) >> 4) * ((w + 15) >> 4);
+    return b < AUG_APPLY_BLOCKS ? b : AUG_APPLY_BLOCKS;
+}
+
+template <typename TS, typename TD>
+void geom_launch_fwd(const void* src, long sn, long sc, long sh, long sw, void* dst, int n, const AugGeom& g, int cp, const float* u,
+                     int policy, const float* table, float* partials, const float* p_dev, hipStream_t s) {
+    int nsl = 0;
+    if (policy & SP_AUG_COLOR) {             // the mean of the RAW input: the existing statistics launch
+        nsl = aug_slices(g.H, g.W, false);
+        const bool run = (sw == 1 && sh == g.W && sc == (long)g.H * g.W) || (sc == 1 && sw == 3 && sh == 3L * g.W);
+        const int dense = run && reinterpret_cast<uintptr_t>(src) % 16 == 0 && (sn * (long)sizeof(TS)) % 16 == 0;
+        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw, g.H, g.W, dense, partials, u, p_dev);
+    }
+    hipLaunchKernelGGL((geom_apply_fwd_kernel<TS, TD>), dim3(geom_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw,
+                       (TD*)dst, g, cp, u, policy, table, partials, nsl, p_dev);
+}
+
+template <typename T>
+void geom_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g, const float* u, int policy, const float* table,
+                     float* partials, const float* p_dev, hipStream_t s) {
+    int nsl = 0;
+    if (policy & SP_AUG_COLOR) {
+        nsl = aug_slices(g.H, g.W, true);
+        hipLaunchKernelGGL(geom_stats_bwd_kernel<T>, dim3(nsl, n), dim3(256), 0, s, (const T*)dy, cp, g, u, policy, table, partials, p_dev);
+    }
+    hipLaunchKernelGGL(geom_apply_bwd_kernel<T>, dim3(geom_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const T*)dy, cp, (T*)dsrc, g, u, policy,
+                       table, partials, nsl, p_dev);
+}
+
 // ---- the gate's controller: 8 words of state {p, r_last, pos, neg, total, steps, adjustments, reserved} ----------------------
 // ONE block of 1024 threads: integer counts, so the result does not depend on any order.  Eight independent 16-byte loads per thread
 // and trip where pred is 16-byte aligned (a single dependent load per trip took 15 us for D's 51 200 predictions); a slot past the end
@@ -428,6 +748,61 @@ extern "C" int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsr
                                            int32_t policy, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(p_dev, "sp_augment_ingest_bwd_gated: p_dev is NULL (the ungated entry is sp_augment_ingest_bwd)");
     return aug_ingest_bwd("sp_augment_ingest_bwd_gated", dy, cp, dsrc, n, h, w_, u, policy, partials, p_dev, dtype, stream);
+}
+
+extern "C" int sp_augment_geom_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out) {
+    SP_CHECK_ARG(slices_out && aug_dims_ok(1, h, w_), "sp_augment_geom_slices: bad args (h=%d w=%d)", h, w_);
+    *slices_out = aug_slices(h, w_, backward != 0);
+    return SP_OK;
+}
+
+extern "C" int sp_augment_geom_decode(const float* u, const float* v, int32_t n, int32_t h, int32_t w_, int32_t policy, int32_t geom,
+                                      float* table, sp_stream_t stream) {
+    SP_CHECK_ARG(u && v && table, "sp_augment_geom_decode: bad args");
+    SP_CHECK_ARG(aug_dims_ok(1, h, w_) && n >= 1 && n <= (1 << 24), "sp_augment_geom_decode: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 2^24)", n, h, w_);
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_geom_decode: bad policy %d", policy);
+    SP_CHECK_ARG(geom >= 1 && geom <= 15, "sp_augment_geom_decode: bad geom %d (an OR of xflip 1, rot90 2, scale 4, rotate 8)", geom);
+    SP_CHECK_ARG(!(geom & SP_GEOM_ROT90) || h == w_, "sp_augment_geom_decode: rot90 needs a square map (h=%d w=%d)", h, w_);
+    hipLaunchKernelGGL(geom_decode_kernel, dim3(sp_div_up((long)n, 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), u, v, n, aug_geom(h, w_),
+                       policy, geom, table);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_augment_geom_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                                      int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, const float* table,
+                                      float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(src && dst && u && table && cp >= 3, "sp_augment_geom_ingest: bad args");
+    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_geom_ingest: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
+    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "sp_augment_geom_ingest: bad dtype");
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_geom_ingest: bad policy %d", policy);
+    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_geom_ingest: the color policy needs the partials buffer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const AugGeom g = aug_geom(h, w_);
+    const int pol = policy & (SP_AUG_COLOR | SP_AUG_CUTOUT);          // the translation is in the table
+    if (src_dtype == SP_F32 && dtype == SP_F32) geom_launch_fwd<float, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
+    else if (src_dtype == SP_F32 && dtype == SP_BF16) geom_launch_fwd<float, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
+    else if (src_dtype == SP_BF16 && dtype == SP_BF16) geom_launch_fwd<bf16, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
+    else geom_launch_fwd<bf16, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_augment_geom_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                                          int32_t policy, const float* table, float* partials, const float* p_dev, int32_t dtype,
+                                          sp_stream_t stream) {
+    SP_CHECK_ARG(dy && dsrc && u && table && cp >= 3, "sp_augment_geom_ingest_bwd: bad args");
+    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_geom_ingest_bwd: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
+    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_augment_geom_ingest_bwd: bad dtype");
+    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_geom_ingest_bwd: bad policy %d", policy);
+    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_geom_ingest_bwd: the color policy needs the partials buffer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const AugGeom g = aug_geom(h, w_);
+    const int pol = policy & (SP_AUG_COLOR | SP_AUG_CUTOUT);
+    if (dtype == SP_F32) geom_launch_bwd<float>(dy, cp, dsrc, n, g, u, pol, table, partials, p_dev, s);
+    else geom_launch_bwd<bf16>(dy, cp, dsrc, n, g, u, pol, table, partials, p_dev, s);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
 }
 
 extern "C" int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream) {

@@ -726,6 +726,11 @@ class Generator(nn.Module):
 # --------------------------------------------------------------------------------------------------
 # discriminator
 # --------------------------------------------------------------------------------------------------
+def _aug_row(row):
+    """One armed row of Discriminator._augment: u alone, or (u, table) with geometric words -> (u, table or None)."""
+    return row if isinstance(row, tuple) else (row, None)
+
+
 class Discriminator(nn.Module):
     """models.py:102-155.  Returns the (B, B, 128) tensor the reference returns."""
 
@@ -754,6 +759,7 @@ class Discriminator(nn.Module):
         # Differentiable augmentation (csrc/augment.hip; beyond the reference): ModelWrapper arms ONE call by setting this to
         # (policy mask, u) for forward or (policy mask, u_a, u_b) for forward_pair and clears it behind the call.  None: the plain ingest.
         # _augment_p rides with it: None, or the gate's probability (a 1-element fp32 device tensor, ops.AdaptiveAugment.p) of that call.
+        # With geometric words each row is a pair (u, table): the batch's affine table of ops.augment_geom_decode.
         self._augment = None
         self._augment_p = None
 
@@ -763,7 +769,8 @@ class Discriminator(nn.Module):
             return ops.ingest_image(input, dt)
         if len(aug) != 2:
             raise ops.L.SempyrError("Discriminator.forward: armed for forward_pair (two rows of uniforms)")
-        return ops.augment_ingest_image(input, dt, aug[1], aug[0], p=getattr(self, "_augment_p", None))
+        u, table = _aug_row(aug[1])
+        return ops.augment_ingest_image(input, dt, u, aug[0], p=getattr(self, "_augment_p", None), table=table)
 
     def forward(self, input: torch.Tensor, class_id: torch.Tensor) -> torch.Tensor:
         dt = ops.compute_dtype()
@@ -827,7 +834,9 @@ class Discriminator(nn.Module):
             if aug is None:
                 x = ops.ingest_image_pair(input_a, input_b, dt)
             else:
-                x = ops.augment_ingest_image_pair(input_a, input_b, dt, aug[1], aug[2], aug[0], p=getattr(self, "_augment_p", None))
+                (u_a, t_a), (u_b, t_b) = _aug_row(aug[1]), _aug_row(aug[2])
+                x = ops.augment_ingest_image_pair(input_a, input_b, dt, u_a, u_b, aug[0], p=getattr(self, "_augment_p", None),
+                                                  table_a=t_a, table_b=t_b)
             x = L[0](x)
             x = L[3](L[2](L[1](x)))
             x = L[7](L[6](L[5](L[4](x))))

@@ -9,6 +9,7 @@ row-major.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -1798,6 +1799,114 @@ def augment_decode(u: torch.Tensor, h: int, w: int, policy=7):
     return o, s, k, ty, tx, cy, cx
 
 
+# the geometric family (csrc/augment.hip: THE GEOMETRIC FAMILY): a SEPARATE mask, so that augment_policy keeps refusing what it refused
+GEOM_XFLIP, GEOM_ROT90, GEOM_SCALE, GEOM_ROTATE = 1, 2, 4, 8
+_GEOM_WORDS = {"xflip": GEOM_XFLIP, "rot90": GEOM_ROT90, "scale": GEOM_SCALE, "rotate": GEOM_ROTATE}
+
+
+def augment_geom(words) -> int:
+    """"xflip,rot90,scale,rotate" (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask of include/sempyr.h's
+    SP_GEOM_*.  An unknown word raises (the words of augment_policy included: augment_split takes both families)."""
+    if words is None:
+        return 0
+    if isinstance(words, int) and not isinstance(words, bool):
+        if not 0 <= words <= 15:
+            raise L.SempyrError("geometric augmentation mask %d: not an OR of xflip (1), rot90 (2), scale (4), rotate (8)" % words)
+        return words
+    if not isinstance(words, str):
+        raise L.SempyrError("geometric augmentation: a comma-separated string of %s (got %r)" % (" / ".join(_GEOM_WORDS), words))
+    mask = 0
+    for word in words.split(","):
+        word = word.strip()
+        if not word:
+            continue
+        if word not in _GEOM_WORDS:
+            raise L.SempyrError("geometric augmentation word %r: choose among %s" % (word, ", ".join(_GEOM_WORDS)))
+        mask |= _GEOM_WORDS[word]
+    return mask
+
+
+def augment_split(policy):
+    """One comma-separated string holding words of both families (or None, or augment_policy's bit mask) -> (policy bits, geom bits).
+    A string without geometric words returns (augment_policy(policy), 0), and raises where augment_policy raises."""
+    if not isinstance(policy, str):
+        return augment_policy(policy), 0
+    words = [w.strip() for w in policy.split(",")]
+    geom = augment_geom(",".join(w for w in words if w in _GEOM_WORDS))
+    return augment_policy(",".join(w for w in words if w not in _GEOM_WORDS)), geom
+
+
+def augment_geom_table(u: torch.Tensor, v: torch.Tensor, h: int, w: int, policy, geom, dtype=torch.float32) -> torch.Tensor:
+    """The decode launch's table ((n, 8): m00 m01 m02 m10 m11 m12 0 0) restated on the host from u (n, 8) and v (n, 4), operation by
+    operation in `dtype`: fp32 gives the kernel's bits for rows without scale and rotate (entries in {-1, 0, 1}, exact offsets) and
+    the kernel's expressions around the host's exp2 / cos / sin otherwise; float64 is the reference of the scale and rotate rows."""
+    policy, geom = augment_policy(policy), augment_geom(geom)
+    u = u.detach().to("cpu", torch.float32)
+    v = v.detach().to("cpu", torch.float32)
+    if u.dim() != 2 or u.shape[1] != 8 or v.dim() != 2 or tuple(v.shape) != (u.shape[0], 4):
+        raise L.SempyrError("augment_geom_table: u must be (n, 8) and v (n, 4), got %s and %s" % (tuple(u.shape), tuple(v.shape)))
+    if geom & GEOM_ROT90 and h != w:
+        raise L.SempyrError("augment_geom_table: rot90 needs a square map (got %d x %d)" % (h, w))
+    n = u.shape[0]
+    const = lambda x: torch.tensor(x, dtype=torch.float32).to(dtype)      # noqa: E731  (the kernel's fp32 constants)
+    vv = v.to(dtype)
+    one, zero = torch.ones(n, dtype=dtype), torch.zeros(n, dtype=dtype)
+    a00, a01, a10, a11 = one, zero, zero, one
+    if geom & (GEOM_SCALE | GEOM_ROTATE):
+        gs, c, s = one, one, zero
+        if geom & GEOM_SCALE:
+            gs = torch.exp2(-(const(0.8) * vv[:, 2] - const(0.4)))
+        if geom & GEOM_ROTATE:
+            theta = (vv[:, 3] - 0.5) * const(math.pi / 2)
+            c, s = torch.cos(theta), torch.sin(theta)
+        a00, a01, a10, a11 = gs * c, -(gs * s), gs * s, gs * c
+    if geom & GEOM_ROT90:
+        k = torch.floor(4.0 * v[:, 1]).to(torch.int64).clamp(max=3)         # fp32, as the kernel
+        for r in range(1, 4):                                               # Q . A: the rows swap, the new second row changes sign
+            sel = k >= r
+            a00, a01, a10, a11 = torch.where(sel, a10, a00), torch.where(sel, a11, a01), torch.where(sel, -a00, a10), torch.where(sel, -a01, a11)
+    if geom & GEOM_XFLIP:
+        flip = v[:, 0] < 0.5
+        a10, a11 = torch.where(flip, -a10, a10), torch.where(flip, -a11, a11)
+    ty, tx = augment_decode(u, h, w, policy & AUG_TRANSLATION)[3:5]
+    cy, cx = (h - 1) / 2.0, (w - 1) / 2.0
+    dy, dx = ty.to(dtype) - cy, tx.to(dtype) - cx
+    m02 = (a00 * dy + a01 * dx) + cy
+    m12 = (a10 * dy + a11 * dx) + cx
+    return torch.stack([a00, a01, m02, a10, a11, m12, zero, zero], dim=1)
+
+
+def augment_geom_decode(u: torch.Tensor, v: torch.Tensor, h: int, w: int, policy, geom, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ONE launch (include/sempyr.h: sp_augment_geom_decode): the affine tables of all rows of u (..., 8) and v (..., 4), contiguous fp32
+    on the GPU, for h x w maps -> (rows, 8) fp32 (into `out` if given).  Reads only the policy's translation bit.
+    augment_geom_table restates it on the host."""
+    policy, geom = augment_policy(policy), augment_geom(geom)
+    require_gpu(u)
+    ok = lambda t, k: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() >= 2 and t.shape[-1] == k      # noqa: E731
+    if not (ok(u, 8) and ok(v, 4) and u.shape[:-1] == v.shape[:-1] and u.device == v.device and u.numel() > 0):
+        raise L.SempyrError("augment_geom_decode: u (..., 8) and v (..., 4) must be contiguous fp32 tensors on one GPU with the same leading "
+                            "shape (got %s %s, %s %s)" % (tuple(u.shape), u.dtype, tuple(v.shape), v.dtype))
+    n = u.numel() // 8
+    if out is None:
+        out = torch.empty((n, 8), dtype=torch.float32, device=u.device)
+    elif not (ok(out, 8) and out.numel() == n * 8 and out.device == u.device):
+        raise L.SempyrError("augment_geom_decode: out must be a contiguous fp32 tensor of %d x 8 on u's GPU" % n)
+    L.call("sp_augment_geom_decode", ptr(u), ptr(v), n, h, w, policy, geom, ptr(out), stream())
+    return out
+
+
+def _augment_table(table, n, device):
+    """The affine table of the geometric entries: contiguous fp32 (n, 8) on the images' GPU.  None: the existing entries."""
+    if table is None:
+        return None
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.device == device and table.dtype == torch.float32
+            and tuple(table.shape) == (n, 8) and table.is_contiguous()):
+        raise L.SempyrError("the geometric augmenting ingest takes table as a contiguous fp32 (n, 8) tensor on the images' GPU, one row per "
+                            "image (got %r for %d images)" % (((tuple(table.shape), table.dtype, str(table.device))
+                                                                 if isinstance(table, torch.Tensor) else table), n))
+    return table
+
+
 def _augment_args(img, u, policy):
     require_gpu(img)
     policy = augment_policy(policy)
@@ -1816,10 +1925,17 @@ def augment_slices(h: int, w: int, backward: bool) -> int:
     return int(out.value)
 
 
-def _augment_partials(n, h, w, policy, backward, device):
+def augment_geom_slices(h: int, w: int, backward: bool) -> int:
+    """Partials per image of the geometric entries' statistics launch (include/sempyr.h: sp_augment_geom_slices)."""
+    out = ctypes.c_int64(0)
+    L.call("sp_augment_geom_slices", h, w, 1 if backward else 0, ctypes.byref(out))
+    return int(out.value)
+
+
+def _augment_partials(n, h, w, policy, backward, device, geom=False):
     if not policy & AUG_COLOR:
         return None
-    return torch.empty((n, augment_slices(h, w, backward)), dtype=torch.float32, device=device)
+    return torch.empty((n, (augment_geom_slices if geom else augment_slices)(h, w, backward)), dtype=torch.float32, device=device)
 
 
 def _augment_gate(p, device):
@@ -1833,10 +1949,14 @@ def _augment_gate(p, device):
     return p
 
 
-def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None):
+def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None, table=None):
     n, _, h, w = img.shape
     sn, scs, sh, sw = img.stride()
-    part = _augment_partials(n, h, w, policy, False, img.device)
+    part = _augment_partials(n, h, w, policy, False, img.device, table is not None)
+    if table is not None:
+        L.call("sp_augment_geom_ingest", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(table),
+               ptr(part), ptr(p), sp_dtype(dtype), stream())
+        return
     if p is not None:
         L.call("sp_augment_ingest_gated", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(part),
                ptr(p), sp_dtype(dtype), stream())
@@ -1849,13 +1969,14 @@ class _AugmentIngestFn(torch.autograd.Function):
     """_IngestFn with the augmentation applied in the same pass: T(img; u) -> NHWC with zero-padded channels; gradients flow through T."""
 
     @staticmethod
-    def forward(ctx, img, dtype, u, policy, p=None):
+    def forward(ctx, img, dtype, u, policy, p=None, table=None):
         n, c, h, w = img.shape
         cp = pad_channels(c, dtype)
         y = nhwc_empty(n, cp, h, w, dtype, img.device)
-        _augment_fwd(img, ptr(y), dtype, cp, u, policy, p)
+        _augment_fwd(img, ptr(y), dtype, cp, u, policy, p, table)
         ctx.cfg = (n, h, w, cp, policy, img.dtype)
         ctx.u = u
+        ctx.table = table                  # None: the existing entries; else the geometric ones, whose backward gathers through the same table
         ctx.p = p                          # the gate reads the SAME device value in the backward pass: p is constant through a step
         return y
 
@@ -1864,30 +1985,38 @@ class _AugmentIngestFn(torch.autograd.Function):
         n, h, w, cp, policy, src_dtype = ctx.cfg
         dy = as_nhwc(dy)
         dsrc = nhwc_empty(n, 3, h, w, dy.dtype, dy.device)
-        part = _augment_partials(n, h, w, policy, True, dy.device)
-        if ctx.p is not None:
+        part = _augment_partials(n, h, w, policy, True, dy.device, ctx.table is not None)
+        if ctx.table is not None:
+            L.call("sp_augment_geom_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(ctx.table), ptr(part), ptr(ctx.p),
+                   sp_dtype(dy.dtype), stream())
+        elif ctx.p is not None:
             L.call("sp_augment_ingest_bwd_gated", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), ptr(ctx.p),
                    sp_dtype(dy.dtype), stream())
         else:
             L.call("sp_augment_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), sp_dtype(dy.dtype), stream())
         if dsrc.dtype != src_dtype:
             dsrc = dsrc.to(src_dtype)
-        return dsrc, None, None, None, None
+        return dsrc, None, None, None, None, None
 
 
-def augment_ingest_image(img: torch.Tensor, dtype, u: torch.Tensor, policy, p: Optional[torch.Tensor] = None) -> torch.Tensor:
+def augment_ingest_image(img: torch.Tensor, dtype, u: torch.Tensor, policy, p: Optional[torch.Tensor] = None,
+                         table: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ingest_image(T(img; u), dtype) in the ingest's own pass (csrc/augment.hip): u = (n, 8) fp32 uniforms on the device, one row per
     image, decoded in the kernel (augment_decode restates it); policy = "color,translation,cutout", a subset, or the bit mask.
     p: None, or the gate - a 1-element fp32 device tensor read when the kernels run: image i is transformed iff u[i, 7] < p, else it
-    is ingested as ingest_image does it, bit for bit, forward and backward (AdaptiveAugment.p is such a tensor)."""
+    is ingested as ingest_image does it, bit for bit, forward and backward (AdaptiveAugment.p is such a tensor).
+    table: None, or the (n, 8) affine table of augment_geom_decode: the geometric entries then resample the image through it (bilinear,
+    zero padding; the backward is the adjoint by gather) and take the policy's color and cutout bits only - the translation is in the table."""
     policy = _augment_args(img, u, policy)
-    return _AugmentIngestFn.apply(img, dtype, u, policy, _augment_gate(p, img.device))
+    return _AugmentIngestFn.apply(img, dtype, u, policy, _augment_gate(p, img.device), _augment_table(table, img.shape[0], img.device))
 
 
 def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u_a: torch.Tensor, u_b: torch.Tensor, policy,
-                              p: Optional[torch.Tensor] = None) -> torch.Tensor:
+                              p: Optional[torch.Tensor] = None, table_a: Optional[torch.Tensor] = None,
+                              table_b: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ingest_image_pair with each batch under its own transform: ONE padded NHWC batch [T(a; u_a) | T(b; u_b)], no autograd of
-    its own (the discriminator step needs no image gradient).  p: the gate of augment_ingest_image, for both batches."""
+    its own (the discriminator step needs no image gradient).  p: the gate of augment_ingest_image, for both batches.  table_a /
+    table_b: both None, or each batch's affine table (augment_ingest_image's table)."""
     with torch.no_grad():
         img_a, img_b = img_a.detach(), img_b.detach()
         policy = _augment_args(img_a, u_a, policy)
@@ -1899,8 +2028,11 @@ def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u
         cp = pad_channels(c, dtype)
         y = nhwc_empty(na + img_b.shape[0], cp, h, w, dtype, img_a.device)
         esz = y.element_size()
-        for img, u, off in ((img_a, u_a, 0), (img_b, u_b, na)):
-            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy, p)
+        if (table_a is None) != (table_b is None):
+            raise L.SempyrError("augment_ingest_image_pair: give both tables or none")
+        table_a, table_b = _augment_table(table_a, na, img_a.device), _augment_table(table_b, img_b.shape[0], img_a.device)
+        for img, u, t, off in ((img_a, u_a, table_a, 0), (img_b, u_b, table_b, na)):
+            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy, p, t)
     return y
 
 
