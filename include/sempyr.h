@@ -88,12 +88,14 @@ int sp_version(void);
  *                            1, and the closing piece of an item stores and counts like every other piece - the hand-over's re-read
  *                            path, which otherwise runs only when a block is delayed, on every split launch)
  *   SP_TUNE_CONV_PP_PRIO     bit 0: s_setprio 1 around every MFMA segment of the ping-pong kernel (default 1); bit 1: static priority 1
- *                            for the second-dispatched half of the block */
+ *                            for the second-dispatched half of the block
+ *   SP_TUNE_PAIRSET_SEGMENTS the pair-set kernels (sp_pairset_knn / _cover) cut the column blocks of a row block into this many segments
+ *                            (default: what gives 6144 blocks; always clamped to [1, column blocks]); sp_pairset_workspace follows it */
 enum { SP_TUNE_CONV_TALL = 0, SP_TUNE_IGEMM_DMA = 1, SP_TUNE_WGRAD_ROWS = 2, SP_TUNE_DETERMINISTIC = 3,
        SP_TUNE_SPLITK_TARGET = 4, SP_TUNE_SPLITK_MINSTEPS = 5, SP_TUNE_CONV1X1_DIRECT = 6, SP_TUNE_CONV_SHORT = 7,
        SP_TUNE_WGRAD9_BLOCKS = 8, SP_TUNE_WGRAD_BLOCKS = 9, SP_TUNE_WGRAD_MINSTEPS = 10, SP_TUNE_WGRAD_SMALL_M = 11,
        SP_TUNE_WGRAD_K1_TILE64 = 12, SP_TUNE_WGRAD_ROWS_THIN = 13, SP_TUNE_WGRAD_ROWS_BLOCKS = 14, SP_TUNE_WGRAD_ROWS_SLABS = 15,
-       SP_TUNE_CONV_STAGGER = 16, SP_TUNE_CONV1X1_SPLITK = 17, SP_TUNE_WGRAD1X1 = 18, SP_TUNE_CONV_CIN8 = 19, SP_TUNE_CONV_THINCO = 20, SP_TUNE_CONV_PP = 21, SP_TUNE_CONV_PP_PRIO = 22, SP_TUNE_WGRAD_PP = 23, SP_TUNE_BN_ITERS = 24, SP_TUNE_IGEMM_TILE = 25, SP_TUNE_CONV_PPW = 26, SP_TUNE_LINEAR_KS = 27, SP_TUNE_CONV_PP_SPLIT = 28, SP_TUNE_COUNT = 29 };
+       SP_TUNE_CONV_STAGGER = 16, SP_TUNE_CONV1X1_SPLITK = 17, SP_TUNE_WGRAD1X1 = 18, SP_TUNE_CONV_CIN8 = 19, SP_TUNE_CONV_THINCO = 20, SP_TUNE_CONV_PP = 21, SP_TUNE_CONV_PP_PRIO = 22, SP_TUNE_WGRAD_PP = 23, SP_TUNE_BN_ITERS = 24, SP_TUNE_IGEMM_TILE = 25, SP_TUNE_CONV_PPW = 26, SP_TUNE_LINEAR_KS = 27, SP_TUNE_CONV_PP_SPLIT = 28, SP_TUNE_PAIRSET_SEGMENTS = 29, SP_TUNE_COUNT = 30 };
 int sp_set_tuning(int32_t key, int32_t value);
 const char* sp_last_error_string(void);
 /* Name of the kernel (route) the last sp_conv2d_igemm / sp_conv2d_wgrad* call of THIS thread launched ("" before the first one):
@@ -835,6 +837,48 @@ int sp_inception_prep(const float* x, float* minmax, void* y, int32_t n, int32_t
                       int32_t cp, int32_t dtype, sp_stream_t stream);
 /* F.adaptive_avg_pool2d(Mixed_7c, (1, 1)).view(B, 2048) (frechet_inception_distance.py:38-41): x [n][hw][c] in dtype -> y [n][c] fp32. */
 int sp_global_avgpool_f32(const void* x, float* y, int32_t n, int32_t hw, int32_t c, int32_t dtype, sp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pair-set metrics on two activation sets (metrics.hip; fp32 only, exact fp32 MFMA, the N x M matrix is never stored):
+ *   KID                       Binkowski, Sutherland, Arbel, Gretton 2018, "Demystifying MMD GANs", as StyleGAN2-ADA computes it
+ *                             (Karras et al. 2020, "Training Generative Adversarial Networks with Limited Data": polynomial kernel
+ *                             k(u, v) = (u.v / d + 1)^3 over subsets of m rows)
+ *   precision / recall        Kynkaanniemi, Karras, Laine, Lehtinen, Aila 2019, "Improved Precision and Recall Metric for Assessing
+ *                             Generative Models": closed balls of radius = distance to the k-th nearest neighbour in the own set
+ *   density / coverage        Naeem, Oh, Uh, Choi, Yoo 2020, "Reliable Fidelity and Diversity Metrics for Generative Models"
+ * a: [na][lda], b: [nb][ldb] row-major fp32, d columns read; lda, ldb % 4 == 0, both 16-byte aligned; na, nb <= 2^22, d <= 2^20.
+ * D(i, j) = max(0, (|a_i|^2 + |b_j|^2) - 2 a_i.b_j) in fp32 - the SQUARED Euclidean distance, no square root anywhere (every
+ * comparison is monotone in it); the norms are fp32 sums of squares.  Every output is bit-identical from launch to launch (integer
+ * atomics and fixed-order partials only).  Every launching entry point takes `workspace` (8-byte aligned) of at least
+ * sp_pairset_workspace() bytes; a failed check returns SP_ERR_INVALID with a message before any launch. */
+
+/* Host logic only (callable without a GPU): the scratch bytes of sp_pairset_knn (k >= 1) / sp_pairset_cover (k = 0) on na x nb rows;
+ * sp_pairset_poly3 wants `subsets` times the answer for (m, m, d, 0).
+ *   bytes = round8(4 (na + nb)) + max(round8(4 na S k), 8 ceil(na / 128) ceil(nb / 64))
+ * S = min(ceil(nb / 64), max(1, ceil(6144 / ceil(na / 128)))) segments of the column blocks, or what SP_TUNE_PAIRSET_SEGMENTS forces
+ * (clamped likewise).  k > 16 or k >= nb: SP_ERR_INVALID. */
+int sp_pairset_workspace(int32_t na, int32_t nb, int32_t d, int32_t k, int64_t* bytes);
+/* radius[i] = the k-th smallest of { D(a_i, b_j) : j } (k = 1: the nearest), 1 <= k <= 16.  same != 0: b IS a (same pointer, na == nb)
+ * and j == i is skipped BY INDEX, not by value - a duplicate row is a neighbour at distance 0 (the radii R_i of precision / recall /
+ * coverage: Kynkaanniemi et al. 2019 section 3, Naeem et al. 2020 section 3).  k >= nb, or k >= nb - 1 when same: SP_ERR_INVALID. */
+int sp_pairset_knn(const float* a, int32_t na, int32_t lda, const float* b, int32_t nb, int32_t ldb, int32_t d, int32_t k,
+                   int32_t same, float* radius, void* workspace, int64_t workspace_bytes, sp_stream_t stream);
+/* One pass over the tiles of D:
+ *   row_count[i] = #{ j : D(i, j) <= rad_b[j] }    col_count[j] = #{ i : D(i, j) <= rad_a[i] }    (closed balls, <=, as both papers write)
+ *   row_min[i]   = min_j D(i, j)                   col_min[j]   = min_i D(i, j)
+ * With a = fake, b = real and the radii of two sp_pairset_knn launches: precision = mean [row_count > 0],
+ * density = sum row_count / (k M), recall = mean [col_count > 0], coverage = mean [col_min <= rad_b].
+ * Any output may be NULL; row_count needs rad_b, col_count needs rad_a.  Counts are int32. */
+int sp_pairset_cover(const float* a, int32_t na, int32_t lda, const float* b, int32_t nb, int32_t ldb, int32_t d,
+                     const float* rad_a, const float* rad_b, int32_t* row_count, int32_t* col_count, float* row_min,
+                     float* col_min, void* workspace, int64_t workspace_bytes, sp_stream_t stream);
+/* out[z] = the float64 sum over the m x m pairs (p, q) of subset z of t^3, t = (double)(a_i.b_j) / (double)d + 1.0, the cube two
+ * float64 multiplications; i = idx_a[z * m + p], j = idx_b[z * m + q] (int32 tables on the device; NULL = the first m rows, one
+ * subset only; an index outside [0, src) reads a row of zeros).  skip_diag != 0 leaves out p == q (the positions, not the indices):
+ * the S_xx - diag_xx of the unbiased MMD^2 estimate.  a: [src_a][lda], b: [src_b][ldb].  subsets <= 65535. */
+int sp_pairset_poly3(const float* a, int32_t src_a, int32_t lda, const int32_t* idx_a, const float* b, int32_t src_b, int32_t ldb,
+                     const int32_t* idx_b, int32_t d, int32_t subsets, int32_t m, int32_t skip_diag, double* out,
+                     void* workspace, int64_t workspace_bytes, sp_stream_t stream);
 
 #ifdef __cplusplus
 }

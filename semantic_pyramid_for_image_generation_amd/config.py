@@ -45,6 +45,9 @@ results beyond floating-point summation order.  The kernel library itself reads 
     clip_grad_norm        SP_CLIP_GRAD_NORM      0        clip each network's gradients by their global norm in front of its optimizer step and skip a step whose
                                                           norm is not finite, on the device (optim.Adam(max_grad_norm=...)); inf = monitor and guard,
                                                           never scale; 0 / empty = off: no launch, no allocation, no logged norm (part of the training recipe too)
+    metrics               SP_METRICS             ""       what ModelWrapper.validate() / evaluate() score besides the FID, from the same activations (metrics.py, csrc/metrics.hip,
+                                                          DESIGN.md 17): a comma-separated subset of kid (Kernel Inception Distance) and prdc (precision, recall,
+                                                          density, coverage); empty = off: the FID alone, no launch, no allocation
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -66,6 +69,21 @@ def parse_clip_grad_norm(text) -> float:
     if not value >= 0.0:                                  # negative, or NaN
         raise ValueError("SP_CLIP_GRAD_NORM must be a number >= 0 or inf (0 = off), got %r" % text)
     return value
+
+
+METRIC_NAMES = ("kid", "prdc")
+
+
+def parse_metrics(text) -> tuple:
+    """SP_METRICS / ModelWrapper(metrics=...): "kid,prdc" -> ("kid", "prdc") - a comma-separated subset of METRIC_NAMES (a list or
+    tuple of the words is taken too), returned in METRIC_NAMES' order; empty or None = off: (); an unknown word is an error."""
+    if isinstance(text, (tuple, list)):
+        text = ",".join(text)
+    words = [w.strip() for w in (text or "").split(",") if w.strip()]
+    for w in words:
+        if w not in METRIC_NAMES:
+            raise ValueError("unknown metric %r (SP_METRICS: a comma-separated subset of %s)" % (w, ", ".join(METRIC_NAMES)))
+    return tuple(n for n in METRIC_NAMES if n in words)
 
 
 @dataclass
@@ -100,6 +118,7 @@ class Config:
     augment: str = ""
     augment_p: str = ""
     clip_grad_norm: float = 0.0
+    metrics: str = ""
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -117,7 +136,8 @@ class Config:
                    bn_pair_upsample=_flag("SP_BN_PAIR_UPSAMPLE", True), defer_wgrad_reduce=_flag("SP_DEFER_WGRAD_REDUCE", True),
                    inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0),
                    augment=os.environ.get("SP_AUGMENT", ""), augment_p=os.environ.get("SP_AUGMENT_P", "").strip(),
-                   clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")))
+                   clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")),
+                   metrics=",".join(parse_metrics(os.environ.get("SP_METRICS"))))
 
 
 CFG = Config.from_env()

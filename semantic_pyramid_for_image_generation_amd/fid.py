@@ -51,11 +51,7 @@ def fid_from_activations(real: np.ndarray, fake: np.ndarray, method: str = "eigh
     return frechet_distance(real.mean(axis=0), np.cov(real, rowvar=False), fake.mean(axis=0), np.cov(fake, rowvar=False), method)
 
 
-@torch.no_grad()
-def collect_activations(dataset_real, generator, vgg16, device="cuda", inception=None):
-    """The loop of frechet_inception_distance.py:63-97: per batch the real activations, vgg16(images), randn(B, latent), the
-    generator (in whatever mode the caller left it) on the loader's masks and labels.float(), the fake activations.
-    Returns the two (N, 2048) float32 arrays."""
+def _extractor(inception):
     if inception is None:
         from .config import CFG
         if not CFG.inception_weights:
@@ -65,19 +61,40 @@ def collect_activations(dataset_real, generator, vgg16, device="cuda", inception
     if not callable(inception):
         from .inception import InceptionV3Features
         inception = InceptionV3Features(inception)
+    return inception
+
+
+@torch.no_grad()
+def _collect(dataset_real, generator, vgg16, device, inception, on_device: bool):
+    inception = _extractor(inception)
     latent = generator.module.latent_dimensions if hasattr(generator, "module") else generator.latent_dimensions
+    keep = (lambda t: t) if on_device else (lambda t: t.cpu())
     real, fake = [], []
     for images, labels, masks in dataset_real:
         images = images.to(device)
         masks = [m.to(device) for m in masks]
-        real.append(inception(images).cpu())
+        real.append(keep(inception(images)))
         features_real = vgg16(images)
         noise = torch.randn((images.shape[0], latent), dtype=torch.float32, device=device)
         images_fake = generator(input=noise, features=features_real, masks=masks, class_id=labels.to(device).float())
-        fake.append(inception(images_fake.float()).cpu())
+        fake.append(keep(inception(images_fake.float())))
     if not real:
         raise SempyrError("FID over an empty validation loader")
-    return torch.cat(real).numpy(), torch.cat(fake).numpy()
+    return torch.cat(real), torch.cat(fake)
+
+
+def collect_activations(dataset_real, generator, vgg16, device="cuda", inception=None):
+    """The loop of frechet_inception_distance.py:63-97: per batch the real activations, vgg16(images), randn(B, latent), the
+    generator (in whatever mode the caller left it) on the loader's masks and labels.float(), the fake activations.
+    Returns the two (N, 2048) float32 arrays."""
+    real, fake = _collect(dataset_real, generator, vgg16, device, inception, on_device=False)
+    return real.numpy(), fake.numpy()
+
+
+def collect_activations_device(dataset_real, generator, vgg16, device="cuda", inception=None):
+    """The same loop, run once, with the two (N, 2048) float32 activation sets left ON THE DEVICE (what metrics.py's pair-set
+    kernels read): no host transfer per batch."""
+    return _collect(dataset_real, generator, vgg16, device, inception, on_device=True)
 
 
 @torch.no_grad()
@@ -86,3 +103,17 @@ def frechet_inception_distance(dataset_real, generator, vgg16, device: str = "cu
     or None for config.CFG.inception_weights (SP_INCEPTION_WEIGHTS)."""
     real, fake = collect_activations(dataset_real, generator, vgg16, device=device, inception=inception)
     return fid_from_activations(real, fake)
+
+
+@torch.no_grad()
+def evaluate(dataset_real, generator, vgg16, device: str = "cuda", inception=None, metrics="", nearest_k: int = 5,
+             kid_subsets: int = 100, kid_subset_size: int = 1000, kid_seed: int = 0) -> dict:
+    """ONE pass of the loader loop, every score from its activations: {"fid": ...} as frechet_inception_distance computes it (the
+    same value for the same seed), plus what `metrics` names (config.parse_metrics: "kid" -> "kid"; "prdc" -> "precision",
+    "recall", "density", "coverage") from the activations kept on the device (metrics.py, csrc/metrics.hip)."""
+    from . import metrics as M
+    names = M.parse_metrics(metrics)
+    real, fake = collect_activations_device(dataset_real, generator, vgg16, device=device, inception=inception)
+    out = M.compute(real, fake, names, nearest_k=nearest_k, num_subsets=kid_subsets, max_subset_size=kid_subset_size, seed=kid_seed)
+    out["fid"] = fid_from_activations(real.cpu().numpy(), fake.cpu().numpy())
+    return out

@@ -31,6 +31,9 @@ And ``augment_p`` (or SP_AUGMENT_P; with ``augment`` only): each image in front 
 untouched otherwise (the gate of csrc/augment.hip) - a fixed p, or one steered on the device from D's predictions
 on the real images (ops.AdaptiveAugment: one counting launch inside the D phase, one adjusting launch behind Adam(G), no host sync);
 p and the signal r_t then join the step's results, the log and the checkpoint.  Off by default: every image is transformed, as above.
+And ``metrics`` (or SP_METRICS): besides the FID, ``evaluate()`` scores KID and / or precision, recall, density and coverage from the
+same activations, kept on the device (metrics.py, csrc/metrics.hip); ``validate()`` still returns the FID, keeps
+the dict in ``last_metrics`` and ``train()`` logs its keys beside ``fid``.  Off by default: validate() is exactly what it was.
 """
 from __future__ import annotations
 
@@ -70,7 +73,8 @@ class ModelWrapper(object):
                  generator_ema=None,
                  augment=None,
                  clip_grad_norm=None,
-                 augment_p=None) -> None:
+                 augment_p=None,
+                 metrics=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -130,6 +134,15 @@ class ModelWrapper(object):
         # (SP_AUGMENT_P); "" = off: every image, nothing below exists.  A number in [0, 1]: fixed.  "adaptive" / "adaptive:<target>" or an
         # ops.AdaptiveAugment: steered on the device.  _ada owns the device state; it is allocated HERE, outside any graph's pool.
         self._ada = self._make_augment_p(CFG.augment_p if augment_p is None else augment_p)
+        # metrics: what validate() / evaluate() score besides the FID - a comma-separated subset of kid, prdc (metrics.py, DESIGN.md
+        # section 17); None: CFG.metrics (SP_METRICS); "" = off: validate() is exactly what it is without.  An unknown word is an error
+        # here.  metrics_nearest_k: the k of the precision / recall / density / coverage radii; last_metrics: evaluate()'s last dict.
+        from .config import parse_metrics
+        self.metrics = parse_metrics(CFG.metrics if metrics is None else metrics)
+        self.metrics_nearest_k = 5
+        self.last_metrics = None
+        if self.metrics:
+            self.logger.hyperparameter['metrics'] = ",".join(self.metrics)
         self._d_params = [p for p in self.discriminator.parameters()]
         self._g_params = [p for p in self.generator.parameters()]
         # clip_grad_norm: a threshold > 0 or inf; None: CFG.clip_grad_norm (SP_CLIP_GRAD_NORM - main.py's fixed keywords once more); 0 = off.
@@ -922,6 +935,10 @@ class ModelWrapper(object):
                     fid = self.validate()
                     self.inference(device=device)
                     self.logger.log(metric_name='fid', value=fid)
+                    if self.metrics and self.last_metrics is not None:
+                        for key, value in self.last_metrics.items():
+                            if key != 'fid':
+                                self.logger.log(metric_name=key, value=value)
                     self.logger.log(metric_name='iterations_fid', value=self.progress_bar.n)
                     if self.path_save_metrics is not None:
                         self.logger.save_metrics(self.path_save_metrics)
@@ -988,14 +1005,12 @@ class ModelWrapper(object):
         The Inception-v3 weights are the constructor's ``inception`` or else CFG.inception_weights (SP_INCEPTION_WEIGHTS); with
         neither (or no validation loader) the result is nan.  `device` is accepted for main.py:111's call and ignored: the
         networks run where the generator's parameters are."""
-        src = self._inception if self._inception is not None else (CFG.inception_weights or None)
-        if src is None or self.validation_dataset_fid is None:
+        if self.metrics:
+            return float(self.evaluate(device=device, use_ema=use_ema)["fid"])
+        src = self._fid_extractor()
+        if src is None:
             return float('nan')
         from .fid import frechet_inception_distance
-        from .inception import InceptionV3Features
-        if not isinstance(src, InceptionV3Features):
-            src = InceptionV3Features(src)
-            self._inception = src                  # built once
         dev = next(self.generator.parameters()).device
         with self._ema_scope(use_ema):
             self.generator.eval()
@@ -1006,6 +1021,42 @@ class ModelWrapper(object):
             finally:
                 self.generator.train()
         return float(fid)
+
+    def _fid_extractor(self):
+        """The Inception-v3 extractor of validate() / evaluate(), built once; None without weights or without a validation loader."""
+        src = self._inception if self._inception is not None else (CFG.inception_weights or None)
+        if src is None or self.validation_dataset_fid is None:
+            return None
+        from .inception import InceptionV3Features
+        if not isinstance(src, InceptionV3Features):
+            src = InceptionV3Features(src)
+            self._inception = src                  # built once
+        return src
+
+    @torch.no_grad()
+    def evaluate(self, device: str = 'cuda', use_ema=None) -> Dict[str, float]:
+        """validate() as a dict: "fid" (the same value validate() returns for the same seed) and, from the SAME activations kept on the
+        device, what the wrapper's ``metrics`` name - "kid"; "precision", "recall", "density", "coverage" (fid.evaluate, metrics.py).
+        The same weight-average scope and eval / train handling as validate(); without weights or a loader every value is nan.  The
+        dict is kept in ``last_metrics``."""
+        from .metrics import PRDC_KEYS
+        keys = ["fid"] + (["kid"] if "kid" in self.metrics else []) + (list(PRDC_KEYS) if "prdc" in self.metrics else [])
+        src = self._fid_extractor()
+        if src is None:
+            self.last_metrics = {k: float('nan') for k in keys}
+            return dict(self.last_metrics)
+        from .fid import evaluate
+        dev = next(self.generator.parameters()).device
+        with self._ema_scope(use_ema):
+            self.generator.eval()
+            self.vgg16.eval()
+            try:
+                out = evaluate(dataset_real=self.validation_dataset_fid, generator=self.generator, vgg16=self.vgg16, device=dev,
+                               inception=src, metrics=self.metrics, nearest_k=self.metrics_nearest_k)
+            finally:
+                self.generator.train()
+        self.last_metrics = {k: float(out[k]) for k in keys}
+        return dict(self.last_metrics)
 
     @torch.no_grad()
     def inference(self, device: str = 'cuda', use_ema=None) -> None:

@@ -2430,3 +2430,70 @@ def conv_launch_f8(x8: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor, x_
         _probed("fwd", 2.0 * n * h * w * cin_p * cout * 9, lambda: L.call("sp_conv2d_igemm", ctypes.byref(p), stream()), (3, cin_p, cout, h, w, n))
         return
     L.call("sp_conv2d_igemm", ctypes.byref(p), stream())
+
+
+# ---- pair-set metrics (csrc/metrics.hip): thin calls; metrics.py holds the definitions ------------------------------
+def pairset_workspace_bytes(na: int, nb: int, d: int, k: int) -> int:
+    """sp_pairset_workspace (host logic: works without a GPU); SempyrError with the library's message for k > 16 or k >= nb."""
+    out = ctypes.c_int64(0)
+    L.call("sp_pairset_workspace", na, nb, d, k, ctypes.byref(out))
+    return int(out.value)
+
+
+def _pairset_set(x: torch.Tensor) -> torch.Tensor:
+    require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous() or x.shape[1] % 4 != 0:
+        raise L.SempyrError("pair-set kernels take contiguous fp32 (n, d) tensors with d % 4 == 0 (metrics.py pads), got %s %s"
+                            % (x.dtype, tuple(x.shape)))
+    return x
+
+
+def _pairset_ws(workspace: Optional[torch.Tensor], need: int, device) -> torch.Tensor:
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise L.SempyrError("pair-set workspace of %d bytes needed, %d given" % (need, workspace.numel() * workspace.element_size()))
+    return workspace
+
+
+def pairset_knn(a: torch.Tensor, b: torch.Tensor, k: int, same: bool = False, d: Optional[int] = None, workspace=None) -> torch.Tensor:
+    """radius[i] = k-th smallest squared distance from a_i to the rows of b (same: b is a, the own row skipped by index).  d: the
+    leading columns read (default all)."""
+    a, b = _pairset_set(a), _pairset_set(b)
+    d = a.shape[1] if d is None else d
+    ws = _pairset_ws(workspace, pairset_workspace_bytes(a.shape[0], b.shape[0], d, k), a.device)
+    out = torch.empty(a.shape[0], dtype=torch.float32, device=a.device)
+    L.call("sp_pairset_knn", ptr(a), a.shape[0], a.shape[1], ptr(b), b.shape[0], b.shape[1], d, k, int(same), ptr(out), ptr(ws),
+           ws.numel() * ws.element_size(), stream())
+    return out
+
+
+def pairset_cover(a: torch.Tensor, b: torch.Tensor, rad_a: Optional[torch.Tensor] = None, rad_b: Optional[torch.Tensor] = None,
+                  d: Optional[int] = None, workspace=None):
+    """(row_count, col_count, row_min, col_min) of sp_pairset_cover in one pass; a count is None without its radii."""
+    a, b = _pairset_set(a), _pairset_set(b)
+    d = a.shape[1] if d is None else d
+    na, nb = a.shape[0], b.shape[0]
+    ws = _pairset_ws(workspace, pairset_workspace_bytes(na, nb, d, 0), a.device)
+    row_count = torch.empty(na, dtype=torch.int32, device=a.device) if rad_b is not None else None
+    col_count = torch.empty(nb, dtype=torch.int32, device=a.device) if rad_a is not None else None
+    row_min = torch.empty(na, dtype=torch.float32, device=a.device)
+    col_min = torch.empty(nb, dtype=torch.float32, device=a.device)
+    L.call("sp_pairset_cover", ptr(a), na, a.shape[1], ptr(b), nb, b.shape[1], d, ptr(rad_a), ptr(rad_b), ptr(row_count), ptr(col_count),
+           ptr(row_min), ptr(col_min), ptr(ws), ws.numel() * ws.element_size(), stream())
+    return row_count, col_count, row_min, col_min
+
+
+def pairset_poly3(a: torch.Tensor, idx_a: Optional[torch.Tensor], b: torch.Tensor, idx_b: Optional[torch.Tensor], subsets: int, m: int,
+                  skip_diag: bool, d: Optional[int] = None, workspace=None) -> torch.Tensor:
+    """float64 [subsets]: per subset the sum over its m x m pairs of (a_i.b_j / d + 1)^3; idx_*: int32 (subsets, m) on the device."""
+    a, b = _pairset_set(a), _pairset_set(b)
+    d = a.shape[1] if d is None else d
+    for idx in (idx_a, idx_b):
+        if idx is not None and (idx.dtype != torch.int32 or not idx.is_cuda or not idx.is_contiguous() or idx.numel() != subsets * m):
+            raise L.SempyrError("pair-set index tables are contiguous int32 (subsets, m) device tensors")
+    ws = _pairset_ws(workspace, subsets * pairset_workspace_bytes(m, m, d, 0), a.device)
+    out = torch.empty(subsets, dtype=torch.float64, device=a.device)
+    L.call("sp_pairset_poly3", ptr(a), a.shape[0], a.shape[1], ptr(idx_a), ptr(b), b.shape[0], b.shape[1], ptr(idx_b), d, subsets, m,
+           int(skip_diag), ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream())
+    return out
