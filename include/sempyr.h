@@ -676,6 +676,40 @@ int sp_rec_loss_bwd_levels(const sp_rec_level* levels, int32_t n_levels, const f
 int sp_div_loss_fwd_w(const void* img, int64_t half_elems, const float* z, int64_t half_z, double* acc,
                       float* out2, float weight, int32_t dtype, sp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Hinge and non-saturating logistic adversarial losses, and the LeCam regularizer of the discriminator (Tseng et al., CVPR 2021,
+ * "Regularizing GANs under limited data").  The reference has NO counterpart (it trains with LSGAN, sp_sqerr_loss_*).  DESIGN.md
+ * section 18.  fp32 only: p is a contiguous fp32 tensor of `numel` predictions, numel in [1, 2^24], else refused; a refusal launches
+ * nothing (and leaves the LeCam state as it is).
+ *
+ * sp_gan_loss_fwd   loss[0] = (float)(sum f(p[i]) / numel), kind 0 = hinge, 1 = logistic; role 0 = D on real, 1 = D on fake, 2 = G:
+ *                       hinge     max(0, 1 - p)    max(0, 1 + p)    -p
+ *                       logistic  softplus(-p)     softplus(p)      softplus(-p)      softplus(x) = max(x, 0) + log1pf(expf(-|x|))
+ *                   ONE block: fp32 partial sums in a fixed order, combined in double, rounded once.  No atomics.  A NaN prediction
+ *                   gives a NaN loss.
+ * sp_gan_loss_bwd   dp[i] = c * f'(p[i]),  c = gout[0] / (float)numel (one fp32 division).  Hinge: -c / +c where the argument of max is
+ *                   > 0 strictly, 0 where it is <= 0 (torch's relu convention), -c for G.  Logistic: -/+ c * sigmoid(-/+ p), sigmoid(x)
+ *                   = 1 / (1 + expf(-x)) for x >= 0, e / (1 + e) with e = expf(x) otherwise (no overflow for any finite x).  A NaN
+ *                   prediction gives a NaN dp at that element - never a silent zero.
+ *
+ * THE LECAM STATE.  8 x 4 bytes in device memory (4-byte aligned):
+ *   slot 0 f32 a_real   1 f32 a_fake   2 i32 updates   3 i32 active   4 f32 m_real   5 f32 m_fake   6, 7 zero
+ * sp_lecam_fwd      one block, in this order:  m_r = (float)(sum(pred_real) / numel), m_f likewise (slots 4, 5);  k = updates;
+ *                   if both means are finite:  k < start: a_real = m_r, a_fake = m_f;  else a = fadd(fmul(decay, a), fmul(1.0f - decay, m))
+ *                   (three fp32 roundings, no FMA);  updates = min(k + 1, 2^31 - 1);   active = (k >= start);
+ *                   reg[0] = active ? (float)((double)weight * (S_r + S_f) / numel) : 0,  S_r = sum h(pred_real - a_fake)^2,
+ *                   S_f = sum h(a_real - pred_fake)^2 with the UPDATED anchors, h(x) = x or, rectified != 0, max(x, 0).
+ *                   weight >= 0 finite, decay in [0, 1), start >= 0, else refused (NaN included).
+ * sp_lecam_bwd      dpred_real[i] = active ? c * h(pred_real[i] - a_fake) : 0,  dpred_fake[i] = active ? -c * h(a_real - pred_fake[i]) : 0,
+ *                   c = gout[0] * weight * (2 / numel) in fp32; the anchors and `active` are read from the state the forward left.
+ * ---------------------------------------------------------------------------------------------- */
+int sp_gan_loss_fwd(const float* p, int64_t numel, int32_t kind, int32_t role, float* loss, sp_stream_t stream);
+int sp_gan_loss_bwd(const float* p, int64_t numel, int32_t kind, int32_t role, const float* gout, float* dp, sp_stream_t stream);
+int sp_lecam_fwd(const float* pred_real, const float* pred_fake, int64_t numel, float weight, float decay, int32_t start,
+                 int32_t rectified, void* state, float* reg, sp_stream_t stream);
+int sp_lecam_bwd(const float* pred_real, const float* pred_fake, int64_t numel, float weight, int32_t rectified, const void* state,
+                 const float* gout, float* dpred_real, float* dpred_fake, sp_stream_t stream);
+
 /* fp8 (OCP e4m3) helpers of the SP_F8 convolution path (BASELINE.json config 5).
  * sp_quantize_fp8: q[i] = e4m3(sat(x[i] * inv_scale[0])) for a bf16 / fp32 tensor of `numel` elements (numel % 16 == 0);
  *   amax (may be NULL): max|x| merged into amax[0].

@@ -48,6 +48,11 @@ results beyond floating-point summation order.  The kernel library itself reads 
     metrics               SP_METRICS             ""       what ModelWrapper.validate() / evaluate() score besides the FID, from the same activations (metrics.py, csrc/metrics.hip,
                                                           DESIGN.md 17): a comma-separated subset of kid (Kernel Inception Distance) and prdc (precision, recall,
                                                           density, coverage); empty = off: the FID alone, no launch, no allocation
+    gan_loss              SP_GAN_LOSS            ""       the adversarial loss pair ModelWrapper installs: lsgan, hinge or logistic (lossfunction.py, csrc/losses.hip,
+                                                          DESIGN.md 18); empty = whatever loss modules its constructor received (LSGAN by default), as before
+    lecam                 SP_LECAM               ""       LeCam regularization of the discriminator (ops.LeCam): weight or weight:decay or weight:decay:start
+                                                          (decay 0.99 and start 1000 by default); empty / 0 = off: no launch, no allocation, no new result (part of the
+                                                          training recipe, as augment is)
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -86,6 +91,58 @@ def parse_metrics(text) -> tuple:
     return tuple(n for n in METRIC_NAMES if n in words)
 
 
+GAN_LOSS_NAMES = ("lsgan", "hinge", "logistic")
+
+
+def parse_gan_loss(text) -> str:
+    """SP_GAN_LOSS / ModelWrapper(gan_loss=...): "" or None = leave the loss modules alone (""); lsgan, hinge or logistic = that pair;
+    anything else is an error."""
+    if text is None:
+        return ""
+    if not isinstance(text, str):
+        raise ValueError("gan_loss takes one of %s or an empty string, got %r" % (", ".join(GAN_LOSS_NAMES), text))
+    text = text.strip()
+    if text and text not in GAN_LOSS_NAMES:
+        raise ValueError("unknown adversarial loss %r (SP_GAN_LOSS: one of %s)" % (text, ", ".join(GAN_LOSS_NAMES)))
+    return text
+
+
+def parse_lecam(spec):
+    """SP_LECAM / ModelWrapper(lecam=...): None, "" or a weight of 0 = off (None); a number = the weight; a string
+    weight[:decay[:start]] -> (weight, decay, start) with decay 0.99 and start 1000 where they are left out.  weight must be finite and
+    >= 0, decay in [0, 1), start an integer >= 0; anything else is an error."""
+    import math
+    bad = ValueError("SP_LECAM takes weight[:decay[:start]] with a finite weight >= 0, decay in [0, 1) and an integer start >= 0 "
+                     "(0 / empty = off), got %r" % (spec,))
+    if spec is None:
+        return None
+    if isinstance(spec, bool) or not isinstance(spec, (int, float, str)):
+        raise bad
+    fields = [f.strip() for f in spec.split(":")] if isinstance(spec, str) else [spec]
+    if isinstance(spec, str) and spec.strip() == "":
+        return None
+    if len(fields) > 3 or any(f == "" for f in fields):
+        raise bad
+    try:
+        weight = float(fields[0])
+        decay = float(fields[1]) if len(fields) > 1 else 0.99
+        start = int(fields[2]) if len(fields) > 2 else 1000
+    except ValueError:
+        raise bad from None
+    if not (0.0 <= weight < math.inf and 0.0 <= decay < 1.0 and 0 <= start < 2 ** 31):
+        raise bad
+    if weight == 0.0:
+        return None
+    return weight, decay, start
+
+
+def _checked_lecam(text) -> str:
+    """The SP_LECAM string as it is, after parse_lecam has accepted it (a malformed value fails at import, as the other parsers do)."""
+    text = (text or "").strip()
+    parse_lecam(text)
+    return text
+
+
 @dataclass
 class Config:
     direct_grads: bool = True
@@ -119,6 +176,8 @@ class Config:
     augment_p: str = ""
     clip_grad_norm: float = 0.0
     metrics: str = ""
+    gan_loss: str = ""
+    lecam: str = ""
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -137,7 +196,8 @@ class Config:
                    inception_weights=os.environ.get("SP_INCEPTION_WEIGHTS", ""), g_ema=float(os.environ.get("SP_G_EMA", "0") or 0),
                    augment=os.environ.get("SP_AUGMENT", ""), augment_p=os.environ.get("SP_AUGMENT_P", "").strip(),
                    clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")),
-                   metrics=",".join(parse_metrics(os.environ.get("SP_METRICS"))))
+                   metrics=",".join(parse_metrics(os.environ.get("SP_METRICS"))),
+                   gan_loss=parse_gan_loss(os.environ.get("SP_GAN_LOSS")), lecam=_checked_lecam(os.environ.get("SP_LECAM")))
 
 
 CFG = Config.from_env()

@@ -378,7 +378,239 @@ __global__ void div_bwd_kernel(const T* __restrict__ img, long half_elems, const
     }
 }
 
+// ---------------- hinge / logistic adversarial losses and the LeCam regularizer (include/sempyr.h) ----------------
+// All four forwards are ONE block of 1024 threads in the shape of sqerr_fwd_small_kernel: four fp32 partial sums per thread over
+// 16-byte loads where the pointer is 16-byte aligned (one fp32 partial over 4-byte loads where it is not), combined in double through
+// wavefront shuffles and 16 LDS slots in a fixed order.  No atomics, no second launch, the same bits on every run.
+enum { GL_HINGE_REAL = 0, GL_HINGE_FAKE = 1, GL_HINGE_GEN = 2, GL_SOFTPLUS_NEG = 3, GL_SOFTPLUS_POS = 4 };
+
+// max(x, 0) that lets a NaN through (fmaxf would return 0): optim.Adam's non-finite guards must see it
+__device__ __forceinline__ float relu_nan(float x) { return x > 0.f ? x : (x <= 0.f ? 0.f : x); }
+__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }      // NaN: 0 + NaN
+__device__ __forceinline__ float sigmoid_f(float x) {                   // no overflow for any finite x; NaN takes the second branch
+    if (x >= 0.f) return __fdiv_rn(1.f, 1.f + expf(-x));
+    const float e = expf(x);
+    return __fdiv_rn(e, 1.f + e);
+}
+// fadd(fmul(decay, a), fmul(c, m)): three fp32 roundings.  HIP's __fmul_rn / __fadd_rn are plain operators, which the compiler's default
+// contraction would fuse into an FMA (one rounding fewer: other bits); the pragma keeps the three operations apart.
+__device__ __forceinline__ float ema_3_roundings(float decay, float a, float c, float m) {
+#pragma clang fp contract(off)
+    const float x = decay * a;
+    const float y = c * m;
+    return x + y;
+}
+template <int MODE>
+struct GanTerm {
+    __device__ __forceinline__ float operator()(float p) const {
+        if (MODE == GL_HINGE_REAL) return relu_nan(1.f - p);
+        if (MODE == GL_HINGE_FAKE) return relu_nan(1.f + p);
+        if (MODE == GL_HINGE_GEN) return -p;
+        return softplus_f(MODE == GL_SOFTPLUS_NEG ? -p : p);
+    }
+};
+struct IdTerm { __device__ __forceinline__ float operator()(float p) const { return p; } };
+// h(sign * (p - anchor))^2: sign +1 for the real predictions against the fake anchor, -1 for the fake ones against the real anchor
+struct LeCamTerm {
+    float anchor, sign; int rectified;
+    __device__ __forceinline__ float operator()(float p) const {
+        float d = sign > 0.f ? p - anchor : anchor - p;
+        if (rectified) d = relu_nan(d);
+        return d * d;
+    }
+};
+
+// this thread's share of sum term(p[i]) of a 1024-thread block, as a double
+template <typename F>
+__device__ __forceinline__ double thread_sum_1024(const float* __restrict__ p, int n, F term) {
+    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    const int n4 = ((reinterpret_cast<uintptr_t>(p) & 15) == 0) ? n / 4 : 0;
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+    int i = threadIdx.x;
+    for (; i + 3 * 1024 < n4; i += 4 * 1024) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = p4[i + u * 1024];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) part[u] += (term(v[u].x) + term(v[u].y)) + (term(v[u].z) + term(v[u].w));
+    }
+    for (; i < n4; i += 1024) {
+        const float4 v = p4[i];
+        part[0] += (term(v.x) + term(v.y)) + (term(v.z) + term(v.w));
+    }
+    int j = n4 * 4 + threadIdx.x;                      // the tail of an aligned pointer (< 4 values), or all of a 4-byte aligned one
+    for (; j + 3 * 1024 < n; j += 4 * 1024) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = p[j + u * 1024];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) part[u] += term(v[u]);
+    }
+    for (; j < n; j += 1024) part[1] += term(p[j]);
+    return ((double)part[0] + (double)part[1]) + ((double)part[2] + (double)part[3]);
+}
+// a, b -> their sums over the block, in EVERY thread (each adds the 16 wavefront totals in the same order)
+__device__ __forceinline__ void block_sum2_1024(double& a, double& b, double (*red)[16]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+    __syncthreads();                                   // (an earlier call's totals may still be being read)
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
+    __syncthreads();
+    double ta = 0.0, tb = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { ta += red[0][k]; tb += red[1][k]; }
+    a = ta; b = tb;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(1024) void gan_loss_fwd_kernel(const float* __restrict__ p, int n, float* __restrict__ loss) {
+    __shared__ double red[2][16];
+    double s = thread_sum_1024(p, n, GanTerm<MODE>()), unused = 0.0;
+    block_sum2_1024(s, unused, red);
+    if (threadIdx.x == 0) loss[0] = (float)(s / (double)n);
+}
+
+template <int MODE>
+__device__ __forceinline__ float gan_dterm(float p, float c) {         // c = g / n
+    if (MODE == GL_HINGE_REAL) { const float t = 1.f - p; return t > 0.f ? -c : (t <= 0.f ? 0.f : t); }
+    if (MODE == GL_HINGE_FAKE) { const float t = 1.f + p; return t > 0.f ? c : (t <= 0.f ? 0.f : t); }
+    if (MODE == GL_HINGE_GEN) return p != p ? p : -c;
+    if (MODE == GL_SOFTPLUS_NEG) return -c * sigmoid_f(-p);
+    return c * sigmoid_f(p);
+}
+template <int MODE>
+__global__ void gan_loss_bwd_kernel(const float* __restrict__ p, int n, const float* __restrict__ gout, float* __restrict__ dp) {
+    const float c = __fdiv_rn(gout[0], (float)n);
+    const int n4 = (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(dp)) & 15) == 0) ? n / 4 : 0;
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+    float4* d4 = reinterpret_cast<float4*>(dp);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const float4 v = p4[i];
+        d4[i] = make_float4(gan_dterm<MODE>(v.x, c), gan_dterm<MODE>(v.y, c), gan_dterm<MODE>(v.z, c), gan_dterm<MODE>(v.w, c));
+    }
+    for (int j = n4 * 4 + blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) dp[j] = gan_dterm<MODE>(p[j], c);
+}
+
+// state: {a_real f32, a_fake f32, updates i32, active i32, m_real f32, m_fake f32, 0, 0}.  Every thread reads the three words it needs
+// before anything is written and derives the same new anchors in registers; thread 0 alone stores, at the end.
+__global__ __launch_bounds__(1024) void lecam_fwd_kernel(const float* __restrict__ pr, const float* __restrict__ pf, int n, float weight,
+                                                         float decay, int start, int rectified, int* __restrict__ state,
+                                                         float* __restrict__ reg) {
+    __shared__ double red[2][16];
+    const float* sf = reinterpret_cast<const float*>(state);
+    float a_real = sf[0], a_fake = sf[1];
+    const int k = state[2];
+    double sr = thread_sum_1024(pr, n, IdTerm()), sfk = thread_sum_1024(pf, n, IdTerm());
+    block_sum2_1024(sr, sfk, red);
+    const float m_r = (float)(sr / (double)n), m_f = (float)(sfk / (double)n);
+    int updates = k;
+    if (isfinite(m_r) && isfinite(m_f)) {
+        if (k < start) { a_real = m_r; a_fake = m_f; }
+        else {
+            const float c = __fsub_rn(1.0f, decay);
+            a_real = ema_3_roundings(decay, a_real, c, m_r);
+            a_fake = ema_3_roundings(decay, a_fake, c, m_f);
+        }
+        updates = k == 0x7fffffff ? k : k + 1;
+    }
+    const int active = k >= start ? 1 : 0;
+    double qr = thread_sum_1024(pr, n, LeCamTerm{a_fake, 1.f, rectified}), qf = thread_sum_1024(pf, n, LeCamTerm{a_real, -1.f, rectified});
+    block_sum2_1024(qr, qf, red);
+    if (threadIdx.x == 0) {
+        float* wf = reinterpret_cast<float*>(state);
+        wf[0] = a_real; wf[1] = a_fake; state[2] = updates; state[3] = active; wf[4] = m_r; wf[5] = m_f;
+        reg[0] = active ? (float)((double)weight * (qr + qf) / (double)n) : 0.0f;
+    }
+}
+
+__device__ __forceinline__ float lecam_h(float d, int rectified) { return rectified ? relu_nan(d) : d; }
+__global__ void lecam_bwd_kernel(const float* __restrict__ pr, const float* __restrict__ pf, int n, float weight, int rectified,
+                                 const int* __restrict__ state, const float* __restrict__ gout, float* __restrict__ dr, float* __restrict__ df) {
+    const float* sf = reinterpret_cast<const float*>(state);
+    const float a_real = sf[0], a_fake = sf[1];
+    const bool active = state[3] != 0;
+    const float c = __fmul_rn(__fmul_rn(gout[0], weight), __fdiv_rn(2.0f, (float)n));          // g * weight * (2 / n)
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(pr) | reinterpret_cast<uintptr_t>(pf) | reinterpret_cast<uintptr_t>(dr) | reinterpret_cast<uintptr_t>(df);
+    const int n4 = (bits & 15) == 0 ? n / 4 : 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f), f = r;
+        if (active) {
+            const float4 x = reinterpret_cast<const float4*>(pr)[i], y = reinterpret_cast<const float4*>(pf)[i];
+            r = make_float4(c * lecam_h(x.x - a_fake, rectified), c * lecam_h(x.y - a_fake, rectified), c * lecam_h(x.z - a_fake, rectified),
+                            c * lecam_h(x.w - a_fake, rectified));
+            f = make_float4(-c * lecam_h(a_real - y.x, rectified), -c * lecam_h(a_real - y.y, rectified), -c * lecam_h(a_real - y.z, rectified),
+                            -c * lecam_h(a_real - y.w, rectified));
+        }
+        reinterpret_cast<float4*>(dr)[i] = r;
+        reinterpret_cast<float4*>(df)[i] = f;
+    }
+    for (int j = n4 * 4 + blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+        dr[j] = active ? c * lecam_h(pr[j] - a_fake, rectified) : 0.f;
+        df[j] = active ? -c * lecam_h(a_real - pf[j], rectified) : 0.f;
+    }
+}
+
+inline int gan_mode(int kind, int role) { return kind == 0 ? role : (role == 1 ? GL_SOFTPLUS_POS : GL_SOFTPLUS_NEG); }
+
 }  // namespace
+
+extern "C" int sp_gan_loss_fwd(const float* p, int64_t numel, int32_t kind, int32_t role, float* loss, sp_stream_t stream) {
+    SP_CHECK_ARG(p && loss, "sp_gan_loss_fwd: bad args");
+    SP_CHECK_ARG(numel >= 1 && numel <= (1L << 24), "sp_gan_loss_fwd: numel=%ld (need 1 ... 2^24)", (long)numel);
+    SP_CHECK_ARG((kind == 0 || kind == 1) && role >= 0 && role <= 2, "sp_gan_loss_fwd: kind=%d role=%d (kind 0 hinge / 1 logistic, role 0 D real / 1 D fake / 2 G)", kind, role);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int n = (int)numel;
+    switch (gan_mode(kind, role)) {
+        case GL_HINGE_REAL: hipLaunchKernelGGL(gan_loss_fwd_kernel<GL_HINGE_REAL>, dim3(1), dim3(1024), 0, s, p, n, loss); break;
+        case GL_HINGE_FAKE: hipLaunchKernelGGL(gan_loss_fwd_kernel<GL_HINGE_FAKE>, dim3(1), dim3(1024), 0, s, p, n, loss); break;
+        case GL_HINGE_GEN: hipLaunchKernelGGL(gan_loss_fwd_kernel<GL_HINGE_GEN>, dim3(1), dim3(1024), 0, s, p, n, loss); break;
+        case GL_SOFTPLUS_NEG: hipLaunchKernelGGL(gan_loss_fwd_kernel<GL_SOFTPLUS_NEG>, dim3(1), dim3(1024), 0, s, p, n, loss); break;
+        default: hipLaunchKernelGGL(gan_loss_fwd_kernel<GL_SOFTPLUS_POS>, dim3(1), dim3(1024), 0, s, p, n, loss); break;
+    }
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_gan_loss_bwd(const float* p, int64_t numel, int32_t kind, int32_t role, const float* gout, float* dp, sp_stream_t stream) {
+    SP_CHECK_ARG(p && gout && dp, "sp_gan_loss_bwd: bad args");
+    SP_CHECK_ARG(numel >= 1 && numel <= (1L << 24), "sp_gan_loss_bwd: numel=%ld (need 1 ... 2^24)", (long)numel);
+    SP_CHECK_ARG((kind == 0 || kind == 1) && role >= 0 && role <= 2, "sp_gan_loss_bwd: kind=%d role=%d (kind 0 hinge / 1 logistic, role 0 D real / 1 D fake / 2 G)", kind, role);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int n = (int)numel;
+    const dim3 g(ew_grid((numel + 3) / 4));
+    switch (gan_mode(kind, role)) {
+        case GL_HINGE_REAL: hipLaunchKernelGGL(gan_loss_bwd_kernel<GL_HINGE_REAL>, g, dim3(256), 0, s, p, n, gout, dp); break;
+        case GL_HINGE_FAKE: hipLaunchKernelGGL(gan_loss_bwd_kernel<GL_HINGE_FAKE>, g, dim3(256), 0, s, p, n, gout, dp); break;
+        case GL_HINGE_GEN: hipLaunchKernelGGL(gan_loss_bwd_kernel<GL_HINGE_GEN>, g, dim3(256), 0, s, p, n, gout, dp); break;
+        case GL_SOFTPLUS_NEG: hipLaunchKernelGGL(gan_loss_bwd_kernel<GL_SOFTPLUS_NEG>, g, dim3(256), 0, s, p, n, gout, dp); break;
+        default: hipLaunchKernelGGL(gan_loss_bwd_kernel<GL_SOFTPLUS_POS>, g, dim3(256), 0, s, p, n, gout, dp); break;
+    }
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_lecam_fwd(const float* pred_real, const float* pred_fake, int64_t numel, float weight, float decay, int32_t start,
+                            int32_t rectified, void* state, float* reg, sp_stream_t stream) {
+    SP_CHECK_ARG(pred_real && pred_fake && state && reg, "sp_lecam_fwd: bad args");
+    SP_CHECK_ARG(numel >= 1 && numel <= (1L << 24), "sp_lecam_fwd: numel=%ld (need 1 ... 2^24)", (long)numel);
+    SP_CHECK_ARG(weight >= 0.f && weight <= 3.402823466e38f && decay >= 0.f && decay < 1.f && start >= 0,
+                 "sp_lecam_fwd: weight=%g decay=%g start=%d (need a finite weight >= 0, decay in [0, 1), start >= 0)", (double)weight, (double)decay, start);
+    hipLaunchKernelGGL(lecam_fwd_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pred_real, pred_fake, (int)numel, weight,
+                       decay, start, rectified ? 1 : 0, (int*)state, reg);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_lecam_bwd(const float* pred_real, const float* pred_fake, int64_t numel, float weight, int32_t rectified, const void* state,
+                            const float* gout, float* dpred_real, float* dpred_fake, sp_stream_t stream) {
+    SP_CHECK_ARG(pred_real && pred_fake && state && gout && dpred_real && dpred_fake, "sp_lecam_bwd: bad args");
+    SP_CHECK_ARG(numel >= 1 && numel <= (1L << 24), "sp_lecam_bwd: numel=%ld (need 1 ... 2^24)", (long)numel);
+    SP_CHECK_ARG(weight >= 0.f && weight <= 3.402823466e38f, "sp_lecam_bwd: weight=%g (need a finite weight >= 0)", (double)weight);
+    hipLaunchKernelGGL(lecam_bwd_kernel, dim3(ew_grid((numel + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pred_real, pred_fake,
+                       (int)numel, weight, rectified ? 1 : 0, (const int*)state, gout, dpred_real, dpred_fake);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
 
 extern "C" int sp_dhead_fwd(const void* x, int32_t ldx, const float* emb_sn, const int64_t* cls, const float* wc,
                             const float* bc, float* pred, int32_t batch, int32_t f, int32_t dtype, sp_stream_t stream) {

@@ -54,10 +54,57 @@ class LSGANGeneratorLoss(nn.Module):
 
 
 class LSGANDiscriminatorLoss(nn.Module):
-    """lossfunction.py:140-164."""
+    """lossfunction.py:140-164.  decision_threshold: the prediction that separates "real" from "fake" under this loss - the midpoint of
+    the targets 1 and 0 - around which the adaptive augmentation counts (ops.AdaptiveAugment)."""
+    decision_threshold = 0.5
 
     def __repr__(self):
         return str(self.__class__.__name__)
 
     def forward(self, prediction_real: torch.Tensor, prediction_fake: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         return ops.sqerr_loss(prediction_real, 1.0), ops.sqerr_loss(prediction_fake, 0.0)
+
+
+class _GanLoss(nn.Module):
+    """The hinge and logistic losses below (no counterpart in the reference; forward signatures as its LSGAN modules; ops.gan_loss,
+    DESIGN.md section 18)."""
+    kind = None
+
+    def __repr__(self):
+        return str(self.__class__.__name__)
+
+
+class _GanGeneratorLoss(_GanLoss):
+    def forward(self, prediction_fake: torch.Tensor) -> torch.Tensor:
+        return ops.gan_loss(prediction_fake, self.kind, "g")
+
+
+class _GanDiscriminatorLoss(_GanLoss):
+    decision_threshold = 0.0              # the sign of D(real) is the overfitting statistic of both losses
+
+    def forward(self, prediction_real: torch.Tensor, prediction_fake: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return ops.gan_loss(prediction_real, self.kind, "d_real"), ops.gan_loss(prediction_fake, self.kind, "d_fake")
+
+
+class HingeGeneratorLoss(_GanGeneratorLoss):
+    """mean(-D(fake))."""
+    kind = "hinge"
+
+
+class HingeDiscriminatorLoss(_GanDiscriminatorLoss):
+    """(mean max(0, 1 - D(real)), mean max(0, 1 + D(fake)))."""
+    kind = "hinge"
+
+
+class LogisticGeneratorLoss(_GanGeneratorLoss):
+    """The non-saturating loss: mean softplus(-D(fake))."""
+    kind = "logistic"
+
+
+class LogisticDiscriminatorLoss(_GanDiscriminatorLoss):
+    """(mean softplus(-D(real)), mean softplus(D(fake)))."""
+    kind = "logistic"
+
+
+GAN_LOSSES = {"lsgan": (LSGANGeneratorLoss, LSGANDiscriminatorLoss), "hinge": (HingeGeneratorLoss, HingeDiscriminatorLoss),
+              "logistic": (LogisticGeneratorLoss, LogisticDiscriminatorLoss)}

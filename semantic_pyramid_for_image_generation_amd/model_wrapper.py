@@ -46,7 +46,7 @@ import torch.nn as nn
 
 from . import misc, ops, profiling
 from .config import CFG
-from .lossfunction import DiversityLoss, LSGANDiscriminatorLoss, LSGANGeneratorLoss, SemanticReconstructionLoss
+from .lossfunction import GAN_LOSSES, DiversityLoss, LSGANDiscriminatorLoss, LSGANGeneratorLoss, SemanticReconstructionLoss
 from .models import VGG16, Discriminator, Generator, _class_index
 
 
@@ -74,7 +74,9 @@ class ModelWrapper(object):
                  augment=None,
                  clip_grad_norm=None,
                  augment_p=None,
-                 metrics=None) -> None:
+                 metrics=None,
+                 gan_loss=None,
+                 lecam=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -83,6 +85,18 @@ class ModelWrapper(object):
         self.vgg16 = _unwrap(vgg16) if vgg16 is not None else VGG16()
         self.generator_optimizer = generator_optimizer
         self.discriminator_optimizer = discriminator_optimizer
+        # gan_loss: "lsgan", "hinge" or "logistic" installs this package's pair of adversarial loss modules (lossfunction.GAN_LOSSES); None:
+        # CFG.gan_loss (SP_GAN_LOSS - main.py's fixed keywords); "" = the modules the caller passed, LSGAN by default, as ever.
+        from .config import parse_gan_loss, parse_lecam
+        try:
+            self.gan_loss = parse_gan_loss(CFG.gan_loss if gan_loss is None else gan_loss)
+        except ValueError as exc:
+            raise ops.L.SempyrError(str(exc)) from None
+        if self.gan_loss:
+            if generator_loss is not None or discriminator_loss is not None:
+                raise ops.L.SempyrError("gan_loss=%r installs its own pair of loss modules, but generator_loss / discriminator_loss were "
+                                        "passed as well: give one or the other" % (self.gan_loss,))
+            generator_loss, discriminator_loss = (cls() for cls in GAN_LOSSES[self.gan_loss])
         self.generator_loss = generator_loss if generator_loss is not None else LSGANGeneratorLoss()
         self.discriminator_loss = discriminator_loss if discriminator_loss is not None else LSGANDiscriminatorLoss()
         self.semantic_reconstruction_loss = (semantic_reconstruction_loss if semantic_reconstruction_loss is not None
@@ -134,6 +148,13 @@ class ModelWrapper(object):
         # (SP_AUGMENT_P); "" = off: every image, nothing below exists.  A number in [0, 1]: fixed.  "adaptive" / "adaptive:<target>" or an
         # ops.AdaptiveAugment: steered on the device.  _ada owns the device state; it is allocated HERE, outside any graph's pool.
         self._ada = self._make_augment_p(CFG.augment_p if augment_p is None else augment_p)
+        if self.gan_loss:
+            self.logger.hyperparameter['gan_loss'] = self.gan_loss
+        # lecam: LeCam regularization of the discriminator (ops.LeCam) - a weight, "weight[:decay[:start]]" or an
+        # ops.LeCam; None: CFG.lecam (SP_LECAM); "" / 0 = off: nothing below exists.  _lecam owns the device state (the two anchors); it is
+        # allocated HERE, outside any graph's pool.  _lecam_reg: the regularizer of the last eager discriminator phase.
+        self._lecam = self._make_lecam(CFG.lecam if lecam is None else lecam, parse_lecam)
+        self._lecam_reg = None
         # metrics: what validate() / evaluate() score besides the FID - a comma-separated subset of kid, prdc (metrics.py, DESIGN.md
         # section 17); None: CFG.metrics (SP_METRICS); "" = off: validate() is exactly what it is without.  An unknown word is an error
         # here.  metrics_nearest_k: the k of the precision / recall / density / coverage radii; last_metrics: evaluate()'s last dict.
@@ -313,13 +334,43 @@ class ModelWrapper(object):
                 raise ops.L.SempyrError("augment_p: the gate's state lives on the discriminator's GPU; move the discriminator there first")
             try:
                 if isinstance(spec, str) and (spec == "adaptive" or spec.startswith("adaptive:")):
-                    ada = ops.AdaptiveAugment(device, target=float(spec[9:])) if spec != "adaptive" else ops.AdaptiveAugment(device)
+                    # counted around the D loss module's own decision threshold: 0.5 for LSGAN (and for a foreign module), 0 for hinge / logistic
+                    kw = {"threshold": float(getattr(self.discriminator_loss, "decision_threshold", 0.5))}
+                    ada = ops.AdaptiveAugment(device, target=float(spec[9:]), **kw) if spec != "adaptive" else ops.AdaptiveAugment(device, **kw)
                 else:
                     ada = ops.AdaptiveAugment(device, p=float(spec), adaptive=False)
             except ValueError:
                 raise ops.L.SempyrError("augment_p takes a probability in [0, 1], 'adaptive' or 'adaptive:<target>' (got %r)" % (spec,)) from None
         self.logger.hyperparameter['augment_p'] = str(dict(ada.settings(), p=float(ada.p)) if not ada.adaptive else ada.settings())
         return ada
+
+    def _make_lecam(self, spec, parse):
+        """The constructor's lecam -> an ops.LeCam or None (off)."""
+        if isinstance(spec, ops.LeCam):
+            lecam = spec
+        else:
+            try:
+                fields = parse(spec)
+            except ValueError as exc:
+                raise ops.L.SempyrError(str(exc)) from None
+            if fields is None:
+                return None
+            device = next(self.discriminator.parameters()).device
+            if device.type != "cuda":
+                raise ops.L.SempyrError("lecam: the anchors live on the discriminator's GPU; move the discriminator there first")
+            lecam = ops.LeCam(device, fields[0], decay=fields[1], start=fields[2])
+        self.logger.hyperparameter['lecam'] = str(lecam.settings())
+        return lecam
+
+    def _with_lecam(self, out: Dict[str, torch.Tensor], reg) -> Dict[str, torch.Tensor]:
+        """The step's results plus, with LeCam on ONLY, the regularizer of its discriminator phase and the two anchors (views of the device
+        state, as augment_p is one of the controller's)."""
+        if self._lecam is None:
+            return out
+        out = dict(out)
+        out["loss_discriminator_lecam"] = reg.detach().reshape(())
+        out["lecam_anchor_real"], out["lecam_anchor_fake"] = self._lecam.anchor_real.reshape(()), self._lecam.anchor_fake.reshape(())
+        return out
 
     def _adaptive(self) -> bool:
         return self._ada is not None and self._ada.adaptive
@@ -444,10 +495,20 @@ class ModelWrapper(object):
             # the overfitting signal's counts (sp_ada_observe): one launch on D's fp32 predictions, inside the first captured graph; p
             # itself moves only behind Adam(G) (train_step), so every gate of this step reads the same value
             self._ada.observe(prediction_real)
+        terms = []
+        if self._lecam is not None:
+            # one launch right behind it, inside the first captured graph too: means, anchors and the regularizer, whatever loss module
+            # follows; its gradient joins D's through one more seed (the fp16 mode's scale included)
+            reg = self._lecam(prediction_real.float(), prediction_fake.float())
+            # kept DETACHED: a tensor with its grad_fn would hold this iteration's autograd graph - and the eager-stream gradient
+            # accumulators of the parameters with it - alive into a later capture_graphs(), which must start without any
+            self._lecam_reg = reg.detach()
+            terms = [reg]
         loss_d_real, loss_d_fake = self.discriminator_loss(prediction_real, prediction_fake)
         self._arm_reducer("d")
         # d(real + fake): one seed per loss instead of a sum kernel and autograd's own seed (model_wrapper.py:158-160)
-        torch.autograd.backward([loss_d_real, loss_d_fake], ops.backward_seeds([loss_d_real, loss_d_fake]))
+        terms = [loss_d_real, loss_d_fake] + terms
+        torch.autograd.backward(terms, ops.backward_seeds(terms))
         self._finish_backward("d")
         return features_real, loss_d_real, loss_d_fake
 
@@ -592,9 +653,10 @@ class ModelWrapper(object):
             if self._adaptive():
                 self._ada.adjust(images_real.shape[0])
         self.iterations += 1
-        return self._with_augment_p(self._with_grad_norms({"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
-                                      "loss_generator": loss_g.detach(), "loss_generator_semantic_reconstruction": loss_rec.detach().reshape(()),
-                                      "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()}))
+        out = self._with_augment_p(self._with_grad_norms({"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
+                                     "loss_generator": loss_g.detach(), "loss_generator_semantic_reconstruction": loss_rec.detach().reshape(()),
+                                     "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()}))
+        return self._with_lecam(out, self._lecam_reg)
 
     # ------------------------------------------------------------------------------------------
     def capture_graphs(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1) -> None:
@@ -658,6 +720,7 @@ class ModelWrapper(object):
                 lab_g = cls if isinstance(self.generator, Generator) else st["labels"]
                 feats, l_real, l_fake = self._d_phase(st["images"], lab_d, lab_g, st["masks"], st["noise_d"], st["feats_real"], st["noise_g"],
                                                       st["augment_u"], st["augment_v"], st["augment_t"])
+            st["lecam_reg"] = self._lecam_reg                      # (None with LeCam off) the first graph's static output
             st["d_grads"] = [p.grad for p in self._d_params]
             # second graph: what the generator step can do in front of the discriminator's optimizer step - its forward, unless that rode
             # in the discriminator phase's pass (Generator.forward_pair), the diversity loss and the VGG-16 pass over the fake images
@@ -793,7 +856,7 @@ class ModelWrapper(object):
             if self._adaptive():
                 self._ada.adjust(st["images"].shape[0])             # eager, as the optimizer steps: p moves between replays
         self.iterations += 1
-        return self._with_augment_p(self._with_grad_norms(st["out"]))
+        return self._with_lecam(self._with_augment_p(self._with_grad_norms(st["out"])), st.get("lecam_reg"))
 
     # ------------------------------------------------------------------------------------------
     def _batch_signature(self, images_real, labels, masks):
@@ -909,6 +972,8 @@ class ModelWrapper(object):
             names += ("grad_norm_discriminator", "grad_norm_generator")
         if self._adaptive():                                    # ... and so do the gate's probability and its signal
             names += ("augment_p", "augment_rt")
+        if self._lecam is not None:                             # ... and the regularizer with its two anchors
+            names += ("loss_discriminator_lecam", "lecam_anchor_real", "lecam_anchor_fake")
         for epoch in range(epochs):
             self.generator.train()
             self.discriminator.train()
@@ -954,6 +1019,8 @@ class ModelWrapper(object):
                     checkpoint["generator_ema_state"] = {"decay": ema.decay, "warmup": ema.warmup, "num_updates": ema.num_updates}
                 if self._adaptive():
                     checkpoint["augment_state"] = self._ada.state_dict()
+                if self._lecam is not None:
+                    checkpoint["lecam_state"] = self._lecam.state_dict()
                 torch.save(checkpoint,
                            os.path.join(self.path_save_models, 'checkpoint_{}.pt'.format(str(epoch).zfill(3))))
             self.inference(device=device)
@@ -985,6 +1052,18 @@ class ModelWrapper(object):
                 raise ops.L.SempyrError("load_augment_state(): neither an AdaptiveAugment state nor a checkpoint with an 'augment_state' key")
             state = state["augment_state"]
         self._ada.load_state_dict(state)
+
+    def load_lecam_state(self, checkpoint_or_state) -> None:
+        """Restores the LeCam anchors for a resumed run: a checkpoint of train() (its "lecam_state" key) or an ops.LeCam.state_dict().
+        The device state is written in place: captured graphs stay valid."""
+        if self._lecam is None:
+            raise ops.L.SempyrError("load_lecam_state(): this ModelWrapper has no LeCam regularizer (lecam / SP_LECAM)")
+        state = checkpoint_or_state
+        if "state" not in state:
+            if "lecam_state" not in state:
+                raise ops.L.SempyrError("load_lecam_state(): neither an ops.LeCam state nor a checkpoint with a 'lecam_state' key")
+            state = state["lecam_state"]
+        self._lecam.load_state_dict(state)
 
     def _ema_scope(self, use_ema):
         """The context validate() / inference() run in: the generator's weight average swapped in (ParameterEMA.applied) where one

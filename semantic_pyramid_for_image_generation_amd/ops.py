@@ -2284,6 +2284,130 @@ def sqerr_loss(p, target: float):
     return _SqErrLossFn.apply(p, target)
 
 
+GAN_LOSS_KINDS = {"hinge": 0, "logistic": 1}
+GAN_LOSS_ROLES = {"d_real": 0, "d_fake": 1, "g": 2}
+
+
+class _GanLossFn(torch.autograd.Function):
+    """mean f(p) of the hinge / logistic losses (include/sempyr.h: sp_gan_loss_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, p, kind, role):
+        require_gpu(p)
+        p = p.contiguous().float()
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        L.call("sp_gan_loss_fwd", ptr(p), p.numel(), kind, role, ptr(loss), stream())
+        ctx.kind, ctx.role = kind, role
+        ctx.save_for_backward(p)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        g = g.contiguous().float()
+        dp = torch.empty_like(p)
+        L.call("sp_gan_loss_bwd", ptr(p), p.numel(), ctx.kind, ctx.role, ptr(g), ptr(dp), stream())
+        return dp, None, None
+
+
+def gan_loss(p, kind: str, role: str):
+    """kind "hinge" | "logistic", role "d_real" | "d_fake" | "g": the mean of max(0, 1 -/+ p) / -p, or of softplus(-/+ p) / softplus(-p),
+    over the fp32 predictions p, as a differentiable scalar (LSGAN stays ops.sqerr_loss)."""
+    if kind not in GAN_LOSS_KINDS or role not in GAN_LOSS_ROLES:
+        raise L.SempyrError("gan_loss: kind must be one of %s and role one of %s (got %r, %r)"
+                            % (sorted(GAN_LOSS_KINDS), sorted(GAN_LOSS_ROLES), kind, role))
+    return _GanLossFn.apply(p, GAN_LOSS_KINDS[kind], GAN_LOSS_ROLES[role])
+
+
+class _LeCamFn(torch.autograd.Function):
+    """One forward launch (means, anchors, regularizer) and one backward launch on the LeCam state (sp_lecam_fwd / sp_lecam_bwd)."""
+
+    @staticmethod
+    def forward(ctx, pred_real, pred_fake, lecam):
+        pred_real, pred_fake = pred_real.contiguous(), pred_fake.contiguous()
+        reg = torch.empty((), dtype=torch.float32, device=pred_real.device)
+        L.call("sp_lecam_fwd", ptr(pred_real), ptr(pred_fake), pred_real.numel(), lecam.weight, lecam.decay, lecam.start,
+               int(lecam.rectified), ptr(lecam.state), ptr(reg), stream())
+        ctx.lecam = lecam
+        ctx.save_for_backward(pred_real, pred_fake)
+        return reg
+
+    @staticmethod
+    def backward(ctx, g):
+        pred_real, pred_fake = ctx.saved_tensors
+        lecam = ctx.lecam
+        g = g.contiguous().float()
+        d_real, d_fake = torch.empty_like(pred_real), torch.empty_like(pred_fake)
+        L.call("sp_lecam_bwd", ptr(pred_real), ptr(pred_fake), pred_real.numel(), lecam.weight, int(lecam.rectified), ptr(lecam.state),
+               ptr(g), ptr(d_real), ptr(d_fake), stream())
+        return d_real, d_fake, None
+
+
+class LeCam:
+    """The LeCam regularizer of the discriminator (Tseng et al., CVPR 2021; include/sempyr.h: sp_lecam_fwd / sp_lecam_bwd; DESIGN.md
+    section 18): D's predictions are pulled towards moving averages ("anchors") of its own mean prediction on the opposite class,
+        reg = weight * (mean h(pred_real - a_fake)^2 + mean h(a_real - pred_fake)^2),   h(x) = x, or max(x, 0) if rectified.
+    The state - {a_real, a_fake, updates, active, m_real, m_fake, 0, 0}, 8 x 4 bytes - lives on the device from construction on (never
+    inside a graph's pool), as AdaptiveAugment.state does: nothing syncs with the host and a captured graph follows the anchors.
+        __call__(pred_real, pred_fake)   one launch: the two means, the anchor update (plain assignment of the means during the first
+                        `start` calls, then a = decay * a + (1 - decay) * mean; a call whose means are not finite leaves the anchors and
+                        the count alone), and the regularizer on the UPDATED anchors - 0 during the first `start` calls.  Differentiable
+                        in both predictions (the anchors are constants); the backward reads the state that forward left."""
+
+    def __init__(self, device, weight: float, decay: float = 0.99, start: int = 1000, rectified: bool = False):
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) < math.inf:
+            raise L.SempyrError("LeCam: weight must be a finite number >= 0, got %r" % (weight,))
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:
+            raise L.SempyrError("LeCam: decay must lie in [0, 1), got %r" % (decay,))
+        if isinstance(start, bool) or int(start) != start or not 0 <= start < 2 ** 31:
+            raise L.SempyrError("LeCam: start must be an integer >= 0, got %r" % (start,))
+        self.weight, self.decay, self.start, self.rectified = float(weight), float(decay), int(start), bool(rectified)
+        self.state = torch.zeros(8, dtype=torch.int32, device=device)
+
+    @property
+    def anchor_real(self) -> torch.Tensor:
+        return self.state[0:1].view(torch.float32)
+
+    @property
+    def anchor_fake(self) -> torch.Tensor:
+        return self.state[1:2].view(torch.float32)
+
+    @property
+    def updates(self) -> torch.Tensor:
+        return self.state[2:3]
+
+    def __call__(self, pred_real: torch.Tensor, pred_fake: torch.Tensor) -> torch.Tensor:
+        for t in (pred_real, pred_fake):
+            if not (t.is_cuda and t.device == self.state.device and t.dtype == torch.float32 and t.numel() >= 1):
+                raise L.SempyrError("LeCam: fp32 predictions on the state's GPU (got %s %s)" % (tuple(t.shape), t.dtype))
+        if pred_real.numel() != pred_fake.numel():
+            raise L.SempyrError("LeCam: %d real and %d fake predictions (the two must be as many)" % (pred_real.numel(), pred_fake.numel()))
+        return _LeCamFn.apply(pred_real, pred_fake, self)
+
+    def values(self) -> dict:
+        """Host copy (syncs): for tests and logs."""
+        s = self.state.cpu()
+        f = s.view(torch.float32).tolist()
+        i = s.tolist()
+        return {"anchor_real": f[0], "anchor_fake": f[1], "updates": i[2], "active": i[3], "mean_real": f[4], "mean_fake": f[5]}
+
+    def settings(self) -> dict:
+        return {"weight": self.weight, "decay": self.decay, "start": self.start, "rectified": self.rectified}
+
+    def state_dict(self) -> dict:
+        return dict(self.settings(), state=self.state.detach().cpu().clone())
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restores the device state IN PLACE (captured graphs have its address baked in) and the settings that came with it."""
+        state = sd["state"]
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and tuple(state.shape) == (8,)):
+            raise L.SempyrError("LeCam.load_state_dict: 'state' must be an int32 tensor of 8 words")
+        for key in ("weight", "decay", "start", "rectified"):
+            if key in sd:
+                setattr(self, key, sd[key])
+        self.state.copy_(state)
+
+
 def _level_geometry(t: torch.Tensor):
     if t.dim() == 4:
         n, h, w, c = dims(t)
