@@ -914,6 +914,34 @@ int sp_pairset_poly3(const float* a, int32_t src_a, int32_t lda, const int32_t* 
                      const int32_t* idx_b, int32_t d, int32_t subsets, int32_t m, int32_t skip_diag, double* out,
                      void* workspace, int64_t workspace_bytes, sp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Inception Score on the same main loop (metrics.hip): Salimans, Goodfellow, Zaremba, Cheung, Radford, Chen 2016,
+ * "Improved Techniques for Training GANs", in the split form StyleGAN2-ADA and torch-fidelity compute.  a: [n][lda] rows (the
+ * activations), w: [classes][ldw] class rows (the classifier's weight), bias: [classes]; fp32, d columns read; lda, ldw % 4 == 0, a and w
+ * 16-byte aligned; n, classes <= 2^22, d <= 2^20.  l_ic = (double)(a_i.w_c in fp32 on the exact fp32 MFMA) + (double)bias_c; everything
+ * after that is float64 with exp / log in double.  The n x classes logit matrix is never stored: it is formed once per entry point.
+ * Split s of S holds the rows [floor(s n / S), floor((s + 1) n / S)), n_s of them.  A non-finite logit makes its row's lse and h, and
+ * its split's kl, NaN (the maximum keeps a NaN); the other splits are untouched.  No float atomics, fixed summation order: every output
+ * is bit-identical from launch to launch.  A failed check returns SP_ERR_INVALID with a message before any launch. */
+
+/* Host logic only (callable without a GPU): the scratch bytes that serve both entry points below,
+ *   bytes = max(24 n S_c, 8 splits ceil(ceil(n / splits) / 128) classes)
+ * S_c = min(ceil(classes / 64), max(1, ceil(6144 / ceil(n / 128)))) segments of the class blocks, or what SP_TUNE_PAIRSET_SEGMENTS
+ * forces (clamped likewise): an online-softmax state of three float64 per (row, segment); one float64 per (split, 128-row block of the
+ * split, class).  splits outside [1, 65535] or n < splits: SP_ERR_INVALID. */
+int sp_pairset_softmax_workspace(int32_t n, int32_t classes, int32_t d, int32_t splits, int64_t* bytes);
+/* lse[i] = m_i + log sum_c exp(l_ic - m_i), m_i = max_c l_ic, and h[i] = sum_c p_ic log p_ic, p_ic = exp(l_ic - lse[i]), formed as
+ * (sum_c e_ic l_ic) / (sum_c e_ic) - lse[i] from the online merge of (m, sum e, sum e l) over the class blocks.  float64 [n] each.
+ * Needs the first term of sp_pairset_softmax_workspace (its answer for any `splits` covers it). */
+int sp_pairset_lse(const float* a, int32_t n, int32_t lda, const float* w, int32_t classes, int32_t ldw, const float* bias, int32_t d,
+                   double* lse, double* h, void* workspace, int64_t workspace_bytes, sp_stream_t stream);
+/* colsum[s][c] = sum_{i in split s} exp(l_ic - lse[i]) (float64 [splits][classes]; every row of it sums to n_s) and
+ * kl[s] = (1 / n_s) sum_{i in s} h[i] - sum_c q_sc log q_sc, q_sc = colsum[s][c] / n_s, 0 log 0 = 0 (float64 [splits]); lse and h are
+ * sp_pairset_lse's outputs for the same operands.  exp(kl[s]) is the split's score; the Inception Score is their mean. */
+int sp_pairset_softmax_colsum(const float* a, int32_t n, int32_t lda, const float* w, int32_t classes, int32_t ldw, const float* bias,
+                              int32_t d, const double* lse, const double* h, int32_t splits, double* colsum, double* kl,
+                              void* workspace, int64_t workspace_bytes, sp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,8 +46,9 @@ results beyond floating-point summation order.  The kernel library itself reads 
                                                           norm is not finite, on the device (optim.Adam(max_grad_norm=...)); inf = monitor and guard,
                                                           never scale; 0 / empty = off: no launch, no allocation, no logged norm (part of the training recipe too)
     metrics               SP_METRICS             ""       what ModelWrapper.validate() / evaluate() score besides the FID, from the same activations (metrics.py, csrc/metrics.hip,
-                                                          DESIGN.md 17): a comma-separated subset of kid (Kernel Inception Distance) and prdc (precision, recall,
-                                                          density, coverage); empty = off: the FID alone, no launch, no allocation
+                                                          DESIGN.md 17, 19): a comma-separated subset of kid (Kernel Inception Distance), prdc (precision, recall,
+                                                          density, coverage) and is (Inception Score: inception_score, inception_score_std; needs fc.weight /
+                                                          fc.bias in the Inception state dict); empty = off: the FID alone, no launch, no allocation
     gan_loss              SP_GAN_LOSS            ""       the adversarial loss pair ModelWrapper installs: lsgan, hinge or logistic (lossfunction.py, csrc/losses.hip,
                                                           DESIGN.md 18); empty = whatever loss modules its constructor received (LSGAN by default), as before
     lecam                 SP_LECAM               ""       LeCam regularization of the discriminator (ops.LeCam): weight or weight:decay or weight:decay:start
@@ -76,7 +77,7 @@ def parse_clip_grad_norm(text) -> float:
     return value
 
 
-METRIC_NAMES = ("kid", "prdc")
+METRIC_NAMES = ("kid", "prdc", "is")
 
 
 def parse_metrics(text) -> tuple:

@@ -107,13 +107,21 @@ def frechet_inception_distance(dataset_real, generator, vgg16, device: str = "cu
 
 @torch.no_grad()
 def evaluate(dataset_real, generator, vgg16, device: str = "cuda", inception=None, metrics="", nearest_k: int = 5,
-             kid_subsets: int = 100, kid_subset_size: int = 1000, kid_seed: int = 0) -> dict:
+             kid_subsets: int = 100, kid_subset_size: int = 1000, kid_seed: int = 0, is_splits: int = 10) -> dict:
     """ONE pass of the loader loop, every score from its activations: {"fid": ...} as frechet_inception_distance computes it (the
     same value for the same seed), plus what `metrics` names (config.parse_metrics: "kid" -> "kid"; "prdc" -> "precision",
-    "recall", "density", "coverage") from the activations kept on the device (metrics.py, csrc/metrics.hip)."""
+    "recall", "density", "coverage"; "is" -> "inception_score", "inception_score_std" of the fake set under the extractor's
+    classifier_head) from the activations kept on the device (metrics.py, csrc/metrics.hip)."""
     from . import metrics as M
     names = M.parse_metrics(metrics)
+    inception = _extractor(inception)
+    head = None
+    if "is" in names:
+        head = inception.classifier_head(device) if hasattr(inception, "classifier_head") else None
+        if head is None:                                 # before the loader loop, not after it
+            raise SempyrError("the Inception Score needs the classifier: the Inception-v3 state dict has no fc.weight / fc.bias")
     real, fake = collect_activations_device(dataset_real, generator, vgg16, device=device, inception=inception)
-    out = M.compute(real, fake, names, nearest_k=nearest_k, num_subsets=kid_subsets, max_subset_size=kid_subset_size, seed=kid_seed)
+    out = M.compute(real, fake, names, nearest_k=nearest_k, head=head, is_splits=is_splits, num_subsets=kid_subsets,
+                    max_subset_size=kid_subset_size, seed=kid_seed)
     out["fid"] = fid_from_activations(real.cpu().numpy(), fake.cpu().numpy())
     return out

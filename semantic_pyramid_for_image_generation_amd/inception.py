@@ -4,8 +4,9 @@ The reference builds ``torchvision.models.inception_v3(pretrained=True, transfor
 ``adaptive_avg_pool2d(., 1)`` -> (B, 2048).  ``InceptionV3Features`` restates exactly that network in eval mode, forward only:
 
   * it reads a torchvision-keyed ``inception_v3`` state dict (a path for ``torch.load`` or a dict) - the file torchvision's
-    download leaves in torch's hub cache; ``AuxLogits.*`` (not run in eval mode), ``fc.*`` (computed, never used) and
-    ``num_batches_tracked`` are ignored;
+    download leaves in torch's hub cache; ``AuxLogits.*`` (not run in eval mode) and ``num_batches_tracked`` are ignored;
+    ``fc.weight`` / ``fc.bias`` (the reference computes the logits and never uses them) are no part of the forward either, but are
+    kept as the classifier head of the Inception Score (``classifier_head``, metrics.py, DESIGN.md 19) when both are present;
   * every BasicConv2d (conv without bias -> BatchNorm2d(eps=0.001) -> ReLU) is folded on the host in float64 into packed
     weights [cout][kh*kw][cin_p] in the compute dtype and an fp32 bias, once;
   * ``forward(images)`` takes NCHW fp32 images on the device (any size; they are normalised per image to [-1, 1] and resized
@@ -29,6 +30,7 @@ from ._lib import SempyrError
 BN_EPS = 1e-3
 INPUT_SIZE = 299
 FEATURES = 2048
+CLASSES = 1000                                      # torchvision's classifier, not the TF graph's 1008
 
 
 def _conv_table() -> List[Tuple[str, int, int, Tuple[int, int], int, Tuple[int, int]]]:
@@ -147,6 +149,23 @@ def fold_state_dict(weights) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
     return out
 
 
+def classifier_head(weights) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+    """(fc.weight (1000, 2048), fc.bias (1000,)) as contiguous fp32 host tensors from a torchvision-keyed inception_v3 state dict, or
+    None when it has neither; one without the other, or a mis-shaped one, raises SempyrError naming the key."""
+    sd = _load(weights)
+    want = {"fc.weight": (CLASSES, FEATURES), "fc.bias": (CLASSES,)}
+    have = [k for k in want if k in sd]
+    if not have:
+        return None
+    for key, shape in want.items():
+        if key not in sd:
+            raise SempyrError("Inception-v3 state dict: %s without %s" % (have[0], key))
+        got = tuple(sd[key].shape)
+        if got != shape:
+            raise SempyrError("Inception-v3 state dict: %s has shape %s, expected %s" % (key, got, shape))
+    return sd["fc.weight"].detach().float().contiguous(), sd["fc.bias"].detach().float().contiguous()
+
+
 class InceptionV3Features:
     """(B, 3, H, W) fp32 images -> (B, 2048) fp32 Mixed_7c activations, averaged over 8 x 8 (frechet_inception_distance.py:38-41)."""
 
@@ -155,9 +174,12 @@ class InceptionV3Features:
         ops.sp_dtype(self.dtype)                   # float32 / bfloat16 / float16 only
         self._spec = {name: (cin, cout, k, s, p) for name, cin, cout, k, s, p in CONV_LAYERS}
         self._host = {}
+        weights = _load(weights)
         for name, (w, b) in fold_state_dict(weights).items():
             self._host[name] = (pack_conv(w, self.dtype), b.float().contiguous())
         self._dev = {}                              # device -> {layer: (packed weight, bias)}
+        self._head_host = classifier_head(weights)  # fp32 whatever the compute dtype: the logits of the Inception Score
+        self._head_dev = {}                         # device -> (weight, bias)
 
     # ---- building blocks ------------------------------------------------------------------------------------------------------
     def _params(self, device) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
@@ -165,6 +187,15 @@ class InceptionV3Features:
         if key not in self._dev:
             self._dev[key] = {n: (w.to(device), b.to(device)) for n, (w, b) in self._host.items()}
         return self._dev[key]
+
+    def classifier_head(self, device) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """(fc.weight (1000, 2048), fc.bias (1000,)) in fp32 on `device`, uploaded once; None when the state dict had no fc.*."""
+        if self._head_host is None:
+            return None
+        key = str(device)
+        if key not in self._head_dev:
+            self._head_dev[key] = tuple(t.to(device) for t in self._head_host)
+        return self._head_dev[key]
 
     def _conv(self, name: str, x: torch.Tensor, out: Optional[torch.Tensor] = None, off: int = 0) -> torch.Tensor:
         cin, cout, (kh, kw), s, (ph, pw) = self._spec[name]

@@ -11,6 +11,12 @@ All of them are functions of the two (N, d) activation sets ``fid.collect_activa
                        index: a duplicate row is a neighbour at distance 0); every ball is closed (<=)
                            precision = mean_j [exists i: D(f_j, r_i) <= R_i]      recall   = mean_i [exists j: D(r_i, f_j) <= F_j]
                            density   = sum_j #{i: D(f_j, r_i) <= R_i} / (k M)     coverage = mean_i [min_j D(r_i, f_j) <= R_i]
+    inception_score(acts, weight, bias)
+                       Inception Score (Salimans et al. 2016) of ONE set, in the split form StyleGAN2-ADA and torch-fidelity compute
+                       (DESIGN.md 19): logits l = acts @ weight.T + bias (torchvision's fc: 1000 classes), p = softmax(l) in float64;
+                       split s of S holds the rows [floor(s n / S), floor((s + 1) n / S)); q_s = mean of p over the split;
+                       KL_s = mean_{i in s} sum_c p_ic log p_ic - sum_c q_sc log q_sc;  score_s = exp(KL_s);
+                       inception_score = mean_s score_s, inception_score_std = sqrt(mean_s (score_s - mean)^2)  (numpy.std's default)
 
 D is the squared Euclidean distance in fp32 on the exact fp32 MFMA; no N x M matrix is stored.  There is no host fallback: the
 inputs go to the device and a missing library is an error.  One host synchronisation per call, at the end."""
@@ -27,6 +33,7 @@ from .config import METRIC_NAMES, parse_metrics
 
 NAMES = METRIC_NAMES
 PRDC_KEYS = ("precision", "recall", "density", "coverage")
+IS_KEYS = ("inception_score", "inception_score_std")
 
 
 def _device_set(x, device=None) -> torch.Tensor:
@@ -102,12 +109,49 @@ def kid(real, fake, num_subsets: int = 100, max_subset_size: int = 1000, seed: i
     return float(t / num_subsets / m)
 
 
-def compute(real, fake, names, nearest_k: int = 5, **kid_args) -> Dict[str, float]:
-    """The metrics named in `names` (parse_metrics) as one flat dict: "kid" and / or the four PRDC_KEYS."""
+def inception_kl(acts, weight, bias, splits: int = 10) -> np.ndarray:
+    """KL_s of every split, float64 (splits,) on the host: sp_pairset_lse (log-sum-exp and sum p log p per row), then
+    sp_pairset_softmax_colsum (the marginals and KL per split) - the (n, classes) logit matrix is formed twice and never stored.  One
+    transfer and one synchronisation, at the end.  A non-finite logit makes its split's entry NaN."""
+    acts_t = _device_set(acts, next((t.device for t in (weight, bias) if isinstance(t, torch.Tensor) and t.is_cuda), None))
+    weight_t = _device_set(weight, acts_t.device)
+    d = acts.shape[1]
+    if weight.shape[1] != d:
+        raise SempyrError("inception score: the rows have %d columns, the class rows %d" % (d, weight.shape[1]))
+    if isinstance(bias, np.ndarray):
+        bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+    if bias.dim() != 1 or bias.dtype != torch.float32 or bias.shape[0] != weight_t.shape[0]:
+        raise SempyrError("inception score: the bias is fp32 (%d,), got %s %s" % (weight_t.shape[0], bias.dtype, tuple(bias.shape)))
+    bias_t = bias.to(acts_t.device).contiguous()
+    n, classes = acts_t.shape[0], weight_t.shape[0]
+    need = ops.pairset_softmax_workspace_bytes(n, classes, d, splits)
+    ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=acts_t.device)
+    lse, h = ops.pairset_lse(acts_t, weight_t, bias_t, d=d, workspace=ws)
+    _, kl = ops.pairset_softmax_colsum(acts_t, weight_t, bias_t, lse, h, splits, d=d, workspace=ws)
+    return kl.cpu().numpy()                                      # the one synchronisation
+
+
+def inception_score_from_kl(kl) -> Dict[str, float]:
+    scores = np.exp(np.asarray(kl, dtype=np.float64))
+    return {"inception_score": float(scores.mean()), "inception_score_std": float(scores.std())}       # population form; a NaN split: both NaN
+
+
+def inception_score(acts, weight, bias, splits: int = 10) -> Dict[str, float]:
+    """{"inception_score", "inception_score_std"} of one fp32 (n, d) activation set under the classifier (weight (classes, d), bias)."""
+    return inception_score_from_kl(inception_kl(acts, weight, bias, splits))
+
+
+def compute(real, fake, names, nearest_k: int = 5, head=None, is_splits: int = 10, **kid_args) -> Dict[str, float]:
+    """The metrics named in `names` (parse_metrics) as one flat dict: "kid", the four PRDC_KEYS and / or the two IS_KEYS ("is": of the
+    fake set, under head = (weight, bias) - InceptionV3Features.classifier_head)."""
     out: Dict[str, float] = {}
     names = parse_metrics(names)
+    if "is" in names and head is None:
+        raise SempyrError("the Inception Score needs the classifier: the Inception-v3 state dict has no fc.weight / fc.bias")
     if "kid" in names:
         out["kid"] = kid(real, fake, **kid_args)
     if "prdc" in names:
         out.update(prdc(real, fake, nearest_k=nearest_k))
+    if "is" in names:
+        out.update(inception_score(fake, head[0], head[1], splits=is_splits))
     return out

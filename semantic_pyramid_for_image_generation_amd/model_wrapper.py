@@ -31,8 +31,9 @@ And ``augment_p`` (or SP_AUGMENT_P; with ``augment`` only): each image in front 
 untouched otherwise (the gate of csrc/augment.hip) - a fixed p, or one steered on the device from D's predictions
 on the real images (ops.AdaptiveAugment: one counting launch inside the D phase, one adjusting launch behind Adam(G), no host sync);
 p and the signal r_t then join the step's results, the log and the checkpoint.  Off by default: every image is transformed, as above.
-And ``metrics`` (or SP_METRICS): besides the FID, ``evaluate()`` scores KID and / or precision, recall, density and coverage from the
-same activations, kept on the device (metrics.py, csrc/metrics.hip); ``validate()`` still returns the FID, keeps
+And ``metrics`` (or SP_METRICS): besides the FID, ``evaluate()`` scores KID, precision, recall, density and coverage and / or the
+Inception Score ("is": ``inception_score``, ``inception_score_std`` of the fake set over ``metrics_is_splits`` splits) from the
+same activations, kept on the device (metrics.py, csrc/metrics.hip, DESIGN.md sections 17 and 19); ``validate()`` still returns the FID, keeps
 the dict in ``last_metrics`` and ``train()`` logs its keys beside ``fid``.  Off by default: validate() is exactly what it was.
 """
 from __future__ import annotations
@@ -155,12 +156,14 @@ class ModelWrapper(object):
         # allocated HERE, outside any graph's pool.  _lecam_reg: the regularizer of the last eager discriminator phase.
         self._lecam = self._make_lecam(CFG.lecam if lecam is None else lecam, parse_lecam)
         self._lecam_reg = None
-        # metrics: what validate() / evaluate() score besides the FID - a comma-separated subset of kid, prdc (metrics.py, DESIGN.md
-        # section 17); None: CFG.metrics (SP_METRICS); "" = off: validate() is exactly what it is without.  An unknown word is an error
-        # here.  metrics_nearest_k: the k of the precision / recall / density / coverage radii; last_metrics: evaluate()'s last dict.
+        # metrics: what validate() / evaluate() score besides the FID - a comma-separated subset of kid, prdc, is (metrics.py, DESIGN.md
+        # sections 17, 19); None: CFG.metrics (SP_METRICS); "" = off: validate() is exactly what it is without.  An unknown word is an error
+        # here.  metrics_nearest_k: the k of the precision / recall / density / coverage radii; metrics_is_splits: the splits of the
+        # Inception Score; last_metrics: evaluate()'s last dict.
         from .config import parse_metrics
         self.metrics = parse_metrics(CFG.metrics if metrics is None else metrics)
         self.metrics_nearest_k = 5
+        self.metrics_is_splits = 10
         self.last_metrics = None
         if self.metrics:
             self.logger.hyperparameter['metrics'] = ",".join(self.metrics)
@@ -1115,11 +1118,13 @@ class ModelWrapper(object):
     @torch.no_grad()
     def evaluate(self, device: str = 'cuda', use_ema=None) -> Dict[str, float]:
         """validate() as a dict: "fid" (the same value validate() returns for the same seed) and, from the SAME activations kept on the
-        device, what the wrapper's ``metrics`` name - "kid"; "precision", "recall", "density", "coverage" (fid.evaluate, metrics.py).
+        device, what the wrapper's ``metrics`` name - "kid"; "precision", "recall", "density", "coverage"; "inception_score",
+        "inception_score_std" (of the generated images; needs fc.weight / fc.bias in the Inception state dict) (fid.evaluate, metrics.py).
         The same weight-average scope and eval / train handling as validate(); without weights or a loader every value is nan.  The
         dict is kept in ``last_metrics``."""
-        from .metrics import PRDC_KEYS
+        from .metrics import IS_KEYS, PRDC_KEYS
         keys = ["fid"] + (["kid"] if "kid" in self.metrics else []) + (list(PRDC_KEYS) if "prdc" in self.metrics else [])
+        keys += list(IS_KEYS) if "is" in self.metrics else []
         src = self._fid_extractor()
         if src is None:
             self.last_metrics = {k: float('nan') for k in keys}
@@ -1131,7 +1136,8 @@ class ModelWrapper(object):
             self.vgg16.eval()
             try:
                 out = evaluate(dataset_real=self.validation_dataset_fid, generator=self.generator, vgg16=self.vgg16, device=dev,
-                               inception=src, metrics=self.metrics, nearest_k=self.metrics_nearest_k)
+                               inception=src, metrics=self.metrics, nearest_k=self.metrics_nearest_k,
+                               is_splits=self.metrics_is_splits)
             finally:
                 self.generator.train()
         self.last_metrics = {k: float(out[k]) for k in keys}

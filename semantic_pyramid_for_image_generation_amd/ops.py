@@ -2621,3 +2621,47 @@ def pairset_poly3(a: torch.Tensor, idx_a: Optional[torch.Tensor], b: torch.Tenso
     L.call("sp_pairset_poly3", ptr(a), a.shape[0], a.shape[1], ptr(idx_a), ptr(b), b.shape[0], b.shape[1], ptr(idx_b), d, subsets, m,
            int(skip_diag), ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream())
     return out
+
+
+# ---- Inception Score on the same main loop (csrc/metrics.hip): thin calls; metrics.py holds the definition -------------
+def pairset_softmax_workspace_bytes(n: int, classes: int, d: int, splits: int) -> int:
+    """sp_pairset_softmax_workspace (host logic: works without a GPU); SempyrError with the library's message for n < splits."""
+    out = ctypes.c_int64(0)
+    L.call("sp_pairset_softmax_workspace", n, classes, d, splits, ctypes.byref(out))
+    return int(out.value)
+
+
+def _pairset_head(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, d: Optional[int]):
+    a, w = _pairset_set(a), _pairset_set(w)
+    require_gpu(bias)
+    if bias.dtype != torch.float32 or bias.dim() != 1 or not bias.is_contiguous() or bias.shape[0] != w.shape[0]:
+        raise L.SempyrError("pair-set softmax: the bias is a contiguous fp32 (%d,) tensor, got %s %s" % (w.shape[0], bias.dtype, tuple(bias.shape)))
+    return a, w, bias, (a.shape[1] if d is None else d)
+
+
+def pairset_lse(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, d: Optional[int] = None, workspace=None):
+    """(lse, h), float64 (n,) each: the log-sum-exp of the logits a @ w.T + bias of every row and sum_c p log p of its softmax."""
+    a, w, bias, d = _pairset_head(a, w, bias, d)
+    n = a.shape[0]
+    ws = _pairset_ws(workspace, pairset_softmax_workspace_bytes(n, w.shape[0], d, 1), a.device)
+    lse = torch.empty(n, dtype=torch.float64, device=a.device)
+    h = torch.empty(n, dtype=torch.float64, device=a.device)
+    L.call("sp_pairset_lse", ptr(a), n, a.shape[1], ptr(w), w.shape[0], w.shape[1], ptr(bias), d, ptr(lse), ptr(h), ptr(ws),
+           ws.numel() * ws.element_size(), stream())
+    return lse, h
+
+
+def pairset_softmax_colsum(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, lse: torch.Tensor, h: torch.Tensor, splits: int,
+                           d: Optional[int] = None, workspace=None):
+    """(colsum, kl), float64 (splits, classes) and (splits,): per split the column sums of the softmax and its KL; lse, h: pairset_lse's."""
+    a, w, bias, d = _pairset_head(a, w, bias, d)
+    n, classes = a.shape[0], w.shape[0]
+    for v in (lse, h):
+        if v.dtype != torch.float64 or not v.is_cuda or not v.is_contiguous() or v.numel() != n:
+            raise L.SempyrError("pair-set softmax: lse and h are contiguous float64 (%d,) device tensors" % n)
+    ws = _pairset_ws(workspace, pairset_softmax_workspace_bytes(n, classes, d, splits), a.device)
+    colsum = torch.empty((splits, classes), dtype=torch.float64, device=a.device)
+    kl = torch.empty(splits, dtype=torch.float64, device=a.device)
+    L.call("sp_pairset_softmax_colsum", ptr(a), n, a.shape[1], ptr(w), classes, w.shape[1], ptr(bias), d, ptr(lse), ptr(h), splits,
+           ptr(colsum), ptr(kl), ptr(ws), ws.numel() * ws.element_size(), stream())
+    return colsum, kl
