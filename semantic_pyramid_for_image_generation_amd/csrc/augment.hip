@@ -101,10 +101,13 @@ __device__ __forceinline__ AugImage aug_decode(const float* __restrict__ u, int 
     return a;
 }
 
+// the cutout window holds output position (h, w)
+__device__ __forceinline__ bool aug_in_window(const AugImage& a, int h, int w) { return h >= a.y0 && h < a.y1 && w >= a.x0 && w < a.x1; }
+
 // output position (h, w) shows source pixel (h + ty, w + tx): false where that is outside the frame or (h, w) is in the window
 __device__ __forceinline__ bool aug_live(const AugImage& a, const AugGeom& g, int h, int w) {
     const int hs = h + a.ty, ws = w + a.tx;
-    return hs >= 0 && hs < g.H && ws >= 0 && ws < g.W && !(h >= a.y0 && h < a.y1 && w >= a.x0 && w < a.x1);
+    return hs >= 0 && hs < g.H && ws >= 0 && ws < g.W && !aug_in_window(a, h, w);
 }
 
 // an image's partials, added in slice order by every thread alike (a handful of floats; the loads are wave-uniform)
@@ -132,6 +135,35 @@ __device__ __forceinline__ void aug_st_padded(TD* __restrict__ d, int CP, const 
         VecIO<bf16, 8>::st(reinterpret_cast<bf16*>(d), v);
     } else {
         for (int c = 0; c < CP; ++c) Elem<TD>::st(d + c, c < 3 ? e[c] : 0.f);
+    }
+}
+
+// a dead image, forward (both families): ingest_kernel's values (x * 1 + 0 with scale3 / shift3 NULL: x, and -0 becomes +0) through these
+// kernels' stores - bit for bit what sp_ingest_image writes
+template <typename TS, typename TD>
+__device__ __forceinline__ void aug_dead_fwd(const TS* __restrict__ src, long sn, long sc, long sh, long sw, TD* __restrict__ dst, const AugGeom& g,
+                                             int CP, int n) {
+    const int HW = g.H * g.W;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+        const int h = p / g.W, w = p - h * g.W;
+        const TS* s = src + (long)n * sn + (long)h * sh + (long)w * sw;
+        float e[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc) + 0.f;
+        aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
+    }
+}
+
+// color of one source pixel, forward (both families); M: the contrast's mean (header comment)
+__device__ __forceinline__ void aug_color_fwd(float (&e)[3], const AugImage& a, float M) {
+    float b[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] = e[c] + a.o;
+    const float m = (b[0] + b[1] + b[2]) / 3.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float sat = (b[c] - m) * a.s + m;
+        e[c] = (sat - M) * a.k + M;
     }
 }
 
@@ -180,18 +212,7 @@ __global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict
                                                             const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
-    if (!aug_gate(u, p_dev, n)) {
-        // a dead image: ingest_kernel's values (x * 1 + 0 with scale3 / shift3 NULL: x, and -0 becomes +0) through this kernel's stores
-        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-            const int h = p / g.W, w = p - h * g.W;
-            const TS* s = src + (long)n * sn + (long)h * sh + (long)w * sw;
-            float e[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc) + 0.f;
-            aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
-        }
-        return;
-    }
+    if (!aug_gate(u, p_dev, n)) { aug_dead_fwd(src, sn, sc, sh, sw, dst, g, CP, n); return; }
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const bool color = (policy & SP_AUG_COLOR) != 0;
     float M = 0.f;
@@ -203,17 +224,7 @@ __global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict
             const TS* s = src + (long)n * sn + (long)(h + a.ty) * sh + (long)(w + a.tx) * sw;
 #pragma unroll
             for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc);
-            if (color) {
-                float b[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) b[c] = e[c] + a.o;
-                const float m = (b[0] + b[1] + b[2]) / 3.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float sat = (b[c] - m) * a.s + m;
-                    e[c] = (sat - M) * a.k + M;
-                }
-            }
+            if (color) aug_color_fwd(e, a, M);
         }
         aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
     }
@@ -231,6 +242,34 @@ __device__ __forceinline__ void aug_ld3(const T* __restrict__ p, int CP, float (
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = Elem<T>::ld(p + c);
     }
+}
+
+// one gradient pixel of pitch 3, element by element as ingest_bwd_kernel stores it
+template <typename T>
+__device__ __forceinline__ void aug_st3(T* d, const float (&v)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+}
+
+// a dead image, backward (both families): ingest_bwd_kernel's values (dy * 1 with scale3 NULL) - bit for bit what sp_ingest_image_bwd writes
+template <typename T>
+__device__ __forceinline__ void aug_dead_bwd(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, const AugGeom& g, int n) {
+    const int HW = g.H * g.W;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+        float v[3];
+        aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
+        aug_st3(dsrc + ((long)n * HW + p) * 3, v);
+    }
+}
+
+// color of one source pixel, backward (both families): g1 -> dx; Gm = sum(g1) / (3 H W)
+__device__ __forceinline__ void aug_color_bwd(float (&v)[3], const AugImage& a, float Gm) {
+    float g2[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g2[c] = a.k * v[c] + (1.f - a.k) * Gm;
+    const float m = (g2[0] + g2[1] + g2[2]) / 3.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = a.s * g2[c] + (1.f - a.s) * m;
 }
 
 // ---- statistics, backward: partial sums of g1 = the dy values that reach an input pixel --------------
@@ -264,17 +303,7 @@ __global__ __launch_bounds__(256) void aug_apply_bwd_kernel(const T* __restrict_
                                                             int nsl, const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
-    if (!aug_gate(u, p_dev, n)) {
-        // a dead image: ingest_bwd_kernel's values (dy * 1 with scale3 NULL), element by element as it stores them
-        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-            float v[3];
-            aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
-            T* d = dsrc + ((long)n * HW + p) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
-        }
-        return;
-    }
+    if (!aug_gate(u, p_dev, n)) { aug_dead_bwd(dy, CP, dsrc, g, n); return; }
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const bool color = (policy & SP_AUG_COLOR) != 0;
     float Gm = 0.f;
@@ -283,19 +312,10 @@ __global__ __launch_bounds__(256) void aug_apply_bwd_kernel(const T* __restrict_
         const int h = p / g.W, w = p - h * g.W;
         const int ho = h - a.ty, wo = w - a.tx;      // the output position that shows this input pixel
         float v[3] = {0.f, 0.f, 0.f};
-        if (ho >= 0 && ho < g.H && wo >= 0 && wo < g.W && !(ho >= a.y0 && ho < a.y1 && wo >= a.x0 && wo < a.x1))
+        if (ho >= 0 && ho < g.H && wo >= 0 && wo < g.W && !aug_in_window(a, ho, wo))
             aug_ld3(dy + ((long)n * HW + (long)ho * g.W + wo) * CP, CP, v);
-        if (color) {
-            float g2[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) g2[c] = a.k * v[c] + (1.f - a.k) * Gm;
-            const float m = (g2[0] + g2[1] + g2[2]) / 3.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = a.s * g2[c] + (1.f - a.s) * m;
-        }
-        T* d = dsrc + ((long)n * HW + p) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+        if (color) aug_color_bwd(v, a, Gm);
+        aug_st3(dsrc + ((long)n * HW + p) * 3, v);
     }
 }
 
@@ -308,32 +328,6 @@ inline int aug_apply_blocks(int h, int w) {
 }
 // 3 H W <= 2^24: float(3 H W) is exact, and pixel indices fit an int with room to spare
 inline bool aug_dims_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && 3L * h * w <= (1L << 24); }
-
-template <typename TS, typename TD>
-void aug_launch_fwd(const void* src, long sn, long sc, long sh, long sw, void* dst, int n, const AugGeom& g, int cp, const float* u,
-                    int policy, float* partials, const float* p_dev, hipStream_t s) {
-    int nsl = 0;
-    if (policy & SP_AUG_COLOR) {
-        nsl = aug_slices(g.H, g.W, false);
-        const bool run = (sw == 1 && sh == g.W && sc == (long)g.H * g.W) || (sc == 1 && sw == 3 && sh == 3L * g.W);
-        const int dense = run && reinterpret_cast<uintptr_t>(src) % 16 == 0 && (sn * (long)sizeof(TS)) % 16 == 0;
-        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw, g.H, g.W, dense, partials, u, p_dev);
-    }
-    hipLaunchKernelGGL((aug_apply_fwd_kernel<TS, TD>), dim3(aug_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw,
-                       (TD*)dst, g, cp, u, policy, partials, nsl, p_dev);
-}
-
-template <typename T>
-void aug_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g, const float* u, int policy, float* partials,
-                    const float* p_dev, hipStream_t s) {
-    int nsl = 0;
-    if (policy & SP_AUG_COLOR) {
-        nsl = aug_slices(g.H, g.W, true);
-        hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, n), dim3(256), 0, s, (const T*)dy, cp, g, u, policy, partials, p_dev);
-    }
-    hipLaunchKernelGGL(aug_apply_bwd_kernel<T>, dim3(aug_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const T*)dy, cp, (T*)dsrc, g, u, policy,
-                       partials, nsl, p_dev);
-}
 
 // ---- the geometric family: one 2 x 3 affine map per image, bilinear taps (header comment: THE GEOMETRIC FAMILY) ----------------------
 struct GeomMap { float m00, m01, m02, m10, m11, m12; };
@@ -378,8 +372,6 @@ __device__ __forceinline__ bool geom_tile_pixel(int t, int tiles_w, const AugGeo
     return h < g.H && w < g.W;
 }
 
-__device__ __forceinline__ bool aug_in_window(const AugImage& a, int h, int w) { return h >= a.y0 && h < a.y1 && w >= a.x0 && w < a.x1; }
-
 // decode: one thread per image, n x 8 floats.  Without scale and rotate the linear part is never multiplied: entries in {-1, 0, 1}.
 __global__ __launch_bounds__(64) void geom_decode_kernel(const float* __restrict__ u, const float* __restrict__ v, int n, AugGeom g, int policy,
                                                          int geom, float* __restrict__ table) {
@@ -414,19 +406,6 @@ __global__ __launch_bounds__(64) void geom_decode_kernel(const float* __restrict
     row[6] = 0.f; row[7] = 0.f;
 }
 
-// color of one source pixel (aug_apply_fwd_kernel's expressions)
-__device__ __forceinline__ void geom_color(float (&e)[3], const AugImage& a, float M) {
-    float b[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) b[c] = e[c] + a.o;
-    const float m = (b[0] + b[1] + b[2]) / 3.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float sat = (b[c] - m) * a.s + m;
-        e[c] = (sat - M) * a.k + M;
-    }
-}
-
 // ---- apply, forward: one output pixel per thread, four taps x three channels from the strided source, color per tap -------------------
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw,
@@ -436,18 +415,7 @@ __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restric
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
     const TS* base = src + (long)n * sn;
-    if (!aug_gate(u, p_dev, n)) {
-        // a dead image: aug_apply_fwd_kernel's dead path, value for value
-        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-            const int h = p / g.W, w = p - h * g.W;
-            const TS* s = base + (long)h * sh + (long)w * sw;
-            float e[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc) + 0.f;
-            aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
-        }
-        return;
-    }
+    if (!aug_gate(u, p_dev, n)) { aug_dead_fwd(src, sn, sc, sh, sw, dst, g, CP, n); return; }
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);          // color and cutout only: the entry masks the translation out
     const GeomMap m = geom_map(table, n);
     const bool color = (policy & SP_AUG_COLOR) != 0;
@@ -473,7 +441,7 @@ __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restric
                         const TS* s = base + (long)(ay.i0 + r) * sh + (long)(ax.i0 + q) * sw;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) t[r][q][c] = Elem<TS>::ld(s + c * sc);
-                        if (color) geom_color(t[r][q], a, M);
+                        if (color) aug_color_fwd(t[r][q], a, M);
                     }
                 }
             }
@@ -526,17 +494,7 @@ __global__ __launch_bounds__(256) void geom_apply_bwd_kernel(const T* __restrict
     __shared__ float inv[4];
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
-    if (!aug_gate(u, p_dev, n)) {            // (block-uniform: no thread of a dead image's block reaches the barrier below)
-        // a dead image: aug_apply_bwd_kernel's dead path, value for value
-        for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-            float v[3];
-            aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
-            T* d = dsrc + ((long)n * HW + p) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
-        }
-        return;
-    }
+    if (!aug_gate(u, p_dev, n)) { aug_dead_bwd(dy, CP, dsrc, g, n); return; }      // (block-uniform: no thread of a dead image's block reaches the barrier below)
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const GeomMap m = geom_map(table, n);
     if (threadIdx.x == 0) {                  // the image's L^-1, once per block
@@ -581,17 +539,8 @@ __global__ __launch_bounds__(256) void geom_apply_bwd_kernel(const T* __restrict
                 for (int c = 0; c < 3; ++c) v[c] += wgt * d[c];
             }
         }
-        if (color) {
-            float g2[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) g2[c] = a.k * v[c] + (1.f - a.k) * Gm;
-            const float mm = (g2[0] + g2[1] + g2[2]) / 3.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = a.s * g2[c] + (1.f - a.s) * mm;
-        }
-        T* d = dsrc + ((long)n * HW + p) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Elem<T>::st(d + c, v[c]);
+        if (color) aug_color_bwd(v, a, Gm);
+        aug_st3(dsrc + ((long)n * HW + p) * 3, v);
     }
 }
 
@@ -600,30 +549,93 @@ inline int geom_apply_blocks(int h, int w) {          // one block per 16 x 16 t
     return b < AUG_APPLY_BLOCKS ? b : AUG_APPLY_BLOCKS;
 }
 
+// ---- the host side: ONE checked call path for the three entry families (plain, gated, geometric) ----------------------------------------
+// What an extern "C" entry was given.  Forward: src -> dst with the source's strides.  Backward: src = dy, dst = dsrc, src_dtype = dtype,
+// no strides.  geom: a geometric entry, which resamples through `table`; p_dev NULL: every image is live.
+struct AugCall {
+    const char* name;
+    const void* src; int32_t src_dtype; int64_t sn, sc, sh, sw;
+    void* dst;
+    int32_t n, h, w, cp;
+    const float* u; int32_t policy;
+    bool geom; const float* table;
+    float* partials; const float* p_dev;
+    int32_t dtype; sp_stream_t stream;
+};
+
+// forward: with color the statistics launch (the mean of the RAW input, whatever the family), then the plain or the geometric apply launch
 template <typename TS, typename TD>
-void geom_launch_fwd(const void* src, long sn, long sc, long sh, long sw, void* dst, int n, const AugGeom& g, int cp, const float* u,
-                     int policy, const float* table, float* partials, const float* p_dev, hipStream_t s) {
+void aug_launch_fwd(const AugCall& c, const AugGeom& g) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
+    const TS* src = (const TS*)c.src;
     int nsl = 0;
-    if (policy & SP_AUG_COLOR) {             // the mean of the RAW input: the existing statistics launch
+    if (c.policy & SP_AUG_COLOR) {
         nsl = aug_slices(g.H, g.W, false);
-        const bool run = (sw == 1 && sh == g.W && sc == (long)g.H * g.W) || (sc == 1 && sw == 3 && sh == 3L * g.W);
-        const int dense = run && reinterpret_cast<uintptr_t>(src) % 16 == 0 && (sn * (long)sizeof(TS)) % 16 == 0;
-        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw, g.H, g.W, dense, partials, u, p_dev);
+        const bool run = (c.sw == 1 && c.sh == g.W && c.sc == (long)g.H * g.W) || (c.sc == 1 && c.sw == 3 && c.sh == 3L * g.W);
+        const int dense = run && reinterpret_cast<uintptr_t>(c.src) % 16 == 0 && (c.sn * (long)sizeof(TS)) % 16 == 0;
+        hipLaunchKernelGGL(aug_stats_fwd_kernel<TS>, dim3(nsl, c.n), dim3(256), 0, s, src, c.sn, c.sc, c.sh, c.sw, g.H, g.W, dense, c.partials, c.u, c.p_dev);
     }
-    hipLaunchKernelGGL((geom_apply_fwd_kernel<TS, TD>), dim3(geom_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const TS*)src, sn, sc, sh, sw,
-                       (TD*)dst, g, cp, u, policy, table, partials, nsl, p_dev);
+    if (c.geom) {
+        hipLaunchKernelGGL((geom_apply_fwd_kernel<TS, TD>), dim3(geom_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, src, c.sn, c.sc, c.sh, c.sw,
+                           (TD*)c.dst, g, c.cp, c.u, c.policy, c.table, c.partials, nsl, c.p_dev);
+    } else {
+        hipLaunchKernelGGL((aug_apply_fwd_kernel<TS, TD>), dim3(aug_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, src, c.sn, c.sc, c.sh, c.sw,
+                           (TD*)c.dst, g, c.cp, c.u, c.policy, c.partials, nsl, c.p_dev);
+    }
 }
 
+// backward: the family's statistics launch (the geometric one weighs dy by its taps), then its apply launch
 template <typename T>
-void geom_launch_bwd(const void* dy, int cp, void* dsrc, int n, const AugGeom& g, const float* u, int policy, const float* table,
-                     float* partials, const float* p_dev, hipStream_t s) {
+void aug_launch_bwd(const AugCall& c, const AugGeom& g) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
+    const T* dy = (const T*)c.src;
     int nsl = 0;
-    if (policy & SP_AUG_COLOR) {
+    if (c.policy & SP_AUG_COLOR) {
         nsl = aug_slices(g.H, g.W, true);
-        hipLaunchKernelGGL(geom_stats_bwd_kernel<T>, dim3(nsl, n), dim3(256), 0, s, (const T*)dy, cp, g, u, policy, table, partials, p_dev);
+        if (c.geom) {
+            hipLaunchKernelGGL(geom_stats_bwd_kernel<T>, dim3(nsl, c.n), dim3(256), 0, s, dy, c.cp, g, c.u, c.policy, c.table, c.partials, c.p_dev);
+        } else {
+            hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, c.n), dim3(256), 0, s, dy, c.cp, g, c.u, c.policy, c.partials, c.p_dev);
+        }
     }
-    hipLaunchKernelGGL(geom_apply_bwd_kernel<T>, dim3(geom_apply_blocks(g.H, g.W), n), dim3(256), 0, s, (const T*)dy, cp, (T*)dsrc, g, u, policy,
-                       table, partials, nsl, p_dev);
+    if (c.geom) {
+        hipLaunchKernelGGL(geom_apply_bwd_kernel<T>, dim3(geom_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, dy, c.cp, (T*)c.dst, g, c.u, c.policy,
+                           c.table, c.partials, nsl, c.p_dev);
+    } else {
+        hipLaunchKernelGGL(aug_apply_bwd_kernel<T>, dim3(aug_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, dy, c.cp, (T*)c.dst, g, c.u, c.policy,
+                           c.partials, nsl, c.p_dev);
+    }
+}
+
+// every ingest entry's body: the checks, their messages under the entry's own name, then the launches of its direction
+int aug_run(AugCall c, bool backward) {
+    SP_CHECK_ARG(c.src && c.dst && c.u && (c.table || !c.geom) && c.cp >= 3, "%s: bad args", c.name);
+    SP_CHECK_ARG(aug_dims_ok(c.n, c.h, c.w), "%s: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", c.name, c.n, c.h, c.w);
+    SP_CHECK_ARG((c.src_dtype == SP_F32 || c.src_dtype == SP_BF16) && (c.dtype == SP_F32 || c.dtype == SP_BF16), "%s: bad dtype", c.name);
+    SP_CHECK_ARG(c.policy >= 0 && c.policy <= 7, "%s: bad policy %d", c.name, c.policy);
+    SP_CHECK_ARG(c.partials || !(c.policy & SP_AUG_COLOR), "%s: the color policy needs the partials buffer", c.name);
+    if (c.geom) c.policy &= SP_AUG_COLOR | SP_AUG_CUTOUT;          // the translation is in the table
+    const AugGeom g = aug_geom(c.h, c.w);
+    const bool s32 = c.src_dtype == SP_F32, d32 = c.dtype == SP_F32;
+    if (backward) {
+        if (d32) aug_launch_bwd<float>(c, g);
+        else aug_launch_bwd<bf16>(c, g);
+    } else if (s32) {
+        if (d32) aug_launch_fwd<float, float>(c, g);
+        else aug_launch_fwd<float, bf16>(c, g);
+    } else {
+        if (d32) aug_launch_fwd<bf16, float>(c, g);
+        else aug_launch_fwd<bf16, bf16>(c, g);
+    }
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+// sp_augment_slices and sp_augment_geom_slices: the partials of both families have one size
+int aug_slices_entry(const char* name, int32_t h, int32_t w_, int32_t backward, int64_t* slices_out) {
+    SP_CHECK_ARG(slices_out && aug_dims_ok(1, h, w_), "%s: bad args (h=%d w=%d)", name, h, w_);
+    *slices_out = aug_slices(h, w_, backward != 0);
+    return SP_OK;
 }
 
 // ---- the gate's controller: 8 words of state {p, r_last, pos, neg, total, steps, adjustments, reserved} ----------------------
@@ -684,76 +696,38 @@ __global__ void ada_adjust_kernel(int* __restrict__ state, int interval, float t
     state[6] += 1;
 }
 
-// the bodies of the ungated and gated entry points (p_dev == NULL: ungated)
-int aug_ingest(const char* name, const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst, int32_t n,
-               int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials, const float* p_dev, int32_t dtype,
-               sp_stream_t stream) {
-    SP_CHECK_ARG(src && dst && u && cp >= 3, "%s: bad args", name);
-    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "%s: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", name, n, h, w_);
-    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "%s: bad dtype", name);
-    SP_CHECK_ARG(policy >= 0 && policy <= 7, "%s: bad policy %d", name, policy);
-    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "%s: the color policy needs the partials buffer", name);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const AugGeom g = aug_geom(h, w_);
-    if (src_dtype == SP_F32 && dtype == SP_F32) aug_launch_fwd<float, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
-    else if (src_dtype == SP_F32 && dtype == SP_BF16) aug_launch_fwd<float, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
-    else if (src_dtype == SP_BF16 && dtype == SP_BF16) aug_launch_fwd<bf16, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
-    else aug_launch_fwd<bf16, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, policy, partials, p_dev, s);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
-}
-
-int aug_ingest_bwd(const char* name, const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u, int32_t policy,
-                   float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(dy && dsrc && u && cp >= 3, "%s: bad args", name);
-    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "%s: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", name, n, h, w_);
-    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "%s: bad dtype", name);
-    SP_CHECK_ARG(policy >= 0 && policy <= 7, "%s: bad policy %d", name, policy);
-    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "%s: the color policy needs the partials buffer", name);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const AugGeom g = aug_geom(h, w_);
-    if (dtype == SP_F32) aug_launch_bwd<float>(dy, cp, dsrc, n, g, u, policy, partials, p_dev, s);
-    else aug_launch_bwd<bf16>(dy, cp, dsrc, n, g, u, policy, partials, p_dev, s);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
-}
-
 }  // namespace
 
 extern "C" int sp_augment_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out) {
-    SP_CHECK_ARG(slices_out && aug_dims_ok(1, h, w_), "sp_augment_slices: bad args (h=%d w=%d)", h, w_);
-    *slices_out = aug_slices(h, w_, backward != 0);
-    return SP_OK;
+    return aug_slices_entry("sp_augment_slices", h, w_, backward, slices_out);
+}
+
+extern "C" int sp_augment_geom_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out) {
+    return aug_slices_entry("sp_augment_geom_slices", h, w_, backward, slices_out);
 }
 
 extern "C" int sp_augment_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                  int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
                                  int32_t dtype, sp_stream_t stream) {
-    return aug_ingest("sp_augment_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, partials, nullptr, dtype, stream);
+    return aug_run({"sp_augment_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, false, nullptr, partials, nullptr, dtype, stream}, false);
 }
 
 extern "C" int sp_augment_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                      int32_t policy, float* partials, int32_t dtype, sp_stream_t stream) {
-    return aug_ingest_bwd("sp_augment_ingest_bwd", dy, cp, dsrc, n, h, w_, u, policy, partials, nullptr, dtype, stream);
+    return aug_run({"sp_augment_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, false, nullptr, partials, nullptr, dtype, stream}, true);
 }
 
 extern "C" int sp_augment_ingest_gated(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                        int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
                                        const float* p_dev, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(p_dev, "sp_augment_ingest_gated: p_dev is NULL (the ungated entry is sp_augment_ingest)");
-    return aug_ingest("sp_augment_ingest_gated", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, partials, p_dev, dtype, stream);
+    return aug_run({"sp_augment_ingest_gated", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, false, nullptr, partials, p_dev, dtype, stream}, false);
 }
 
 extern "C" int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                            int32_t policy, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(p_dev, "sp_augment_ingest_bwd_gated: p_dev is NULL (the ungated entry is sp_augment_ingest_bwd)");
-    return aug_ingest_bwd("sp_augment_ingest_bwd_gated", dy, cp, dsrc, n, h, w_, u, policy, partials, p_dev, dtype, stream);
-}
-
-extern "C" int sp_augment_geom_slices(int32_t h, int32_t w_, int32_t backward, int64_t* slices_out) {
-    SP_CHECK_ARG(slices_out && aug_dims_ok(1, h, w_), "sp_augment_geom_slices: bad args (h=%d w=%d)", h, w_);
-    *slices_out = aug_slices(h, w_, backward != 0);
-    return SP_OK;
+    return aug_run({"sp_augment_ingest_bwd_gated", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, false, nullptr, partials, p_dev, dtype, stream}, true);
 }
 
 extern "C" int sp_augment_geom_decode(const float* u, const float* v, int32_t n, int32_t h, int32_t w_, int32_t policy, int32_t geom,
@@ -772,37 +746,13 @@ extern "C" int sp_augment_geom_decode(const float* u, const float* v, int32_t n,
 extern "C" int sp_augment_geom_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                       int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, const float* table,
                                       float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
-    SP_CHECK_ARG(src && dst && u && table && cp >= 3, "sp_augment_geom_ingest: bad args");
-    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_geom_ingest: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
-    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "sp_augment_geom_ingest: bad dtype");
-    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_geom_ingest: bad policy %d", policy);
-    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_geom_ingest: the color policy needs the partials buffer");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const AugGeom g = aug_geom(h, w_);
-    const int pol = policy & (SP_AUG_COLOR | SP_AUG_CUTOUT);          // the translation is in the table
-    if (src_dtype == SP_F32 && dtype == SP_F32) geom_launch_fwd<float, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
-    else if (src_dtype == SP_F32 && dtype == SP_BF16) geom_launch_fwd<float, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
-    else if (src_dtype == SP_BF16 && dtype == SP_BF16) geom_launch_fwd<bf16, bf16>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
-    else geom_launch_fwd<bf16, float>(src, sn, sc, sh, sw, dst, n, g, cp, u, pol, table, partials, p_dev, s);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    return aug_run({"sp_augment_geom_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, true, table, partials, p_dev, dtype, stream}, false);
 }
 
 extern "C" int sp_augment_geom_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                           int32_t policy, const float* table, float* partials, const float* p_dev, int32_t dtype,
                                           sp_stream_t stream) {
-    SP_CHECK_ARG(dy && dsrc && u && table && cp >= 3, "sp_augment_geom_ingest_bwd: bad args");
-    SP_CHECK_ARG(aug_dims_ok(n, h, w_), "sp_augment_geom_ingest_bwd: n=%d h=%d w=%d (need 3*h*w <= 2^24, n <= 65535)", n, h, w_);
-    SP_CHECK_ARG(dtype == SP_F32 || dtype == SP_BF16, "sp_augment_geom_ingest_bwd: bad dtype");
-    SP_CHECK_ARG(policy >= 0 && policy <= 7, "sp_augment_geom_ingest_bwd: bad policy %d", policy);
-    SP_CHECK_ARG(partials || !(policy & SP_AUG_COLOR), "sp_augment_geom_ingest_bwd: the color policy needs the partials buffer");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const AugGeom g = aug_geom(h, w_);
-    const int pol = policy & (SP_AUG_COLOR | SP_AUG_CUTOUT);
-    if (dtype == SP_F32) geom_launch_bwd<float>(dy, cp, dsrc, n, g, u, pol, table, partials, p_dev, s);
-    else geom_launch_bwd<bf16>(dy, cp, dsrc, n, g, u, pol, table, partials, p_dev, s);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    return aug_run({"sp_augment_geom_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, true, table, partials, p_dev, dtype, stream}, true);
 }
 
 extern "C" int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream) {

@@ -404,34 +404,30 @@ class ModelWrapper(object):
         data parallelism the discriminator's gradient all-reduce then hides behind _g_features instead of the generator forward.)"""
         return CFG.g_pair and isinstance(self.generator, Generator) and self.generator.training
 
-    def _augment_rows(self, images_real, augment_u):
-        """The step's (3, B, 8) uniforms - row 0: the real images of the D step, 1: its fake images, 2: the fake images of the G step in
-        front of D - or None with augmentation off.  Drawn FIRST in a step (before the latents) unless the caller brings them."""
-        if not (self._aug_policy or self._aug_geom):
-            if augment_u is not None:
-                raise ops.L.SempyrError("augment_u given, but this ModelWrapper augments nothing (augment / SP_AUGMENT)")
+    def _uniform_rows(self, images_real, given, width, on, name, off_text):
+        """The step's (3, B, width) uniforms - row 0: the real images of the D step, 1: its fake images, 2: the fake images of the G step in
+        front of D - drawn here unless the caller brings them (`given`), or None where `on` is false (then bringing them raises)."""
+        if not on:
+            if given is not None:
+                raise ops.L.SempyrError("%s given, but this ModelWrapper %s" % (name, off_text))
             return None
-        shape = (3, images_real.shape[0], 8)
-        if augment_u is None:
+        shape = (3, images_real.shape[0], width)
+        if given is None:
             return torch.rand(shape, dtype=torch.float32, device=images_real.device)
-        if tuple(augment_u.shape) != shape:
-            raise ops.L.SempyrError("augment_u must be %s (three transforms x batch x 8 uniforms), got %s" % (shape, tuple(augment_u.shape)))
-        return augment_u.detach().to(device=images_real.device, dtype=torch.float32).contiguous()
+        if tuple(given.shape) != shape:
+            raise ops.L.SempyrError("%s must be %s (three transforms x batch x %d uniforms), got %s" % (name, shape, width, tuple(given.shape)))
+        return given.detach().to(device=images_real.device, dtype=torch.float32).contiguous()
+
+    def _augment_rows(self, images_real, augment_u):
+        """The step's (3, B, 8) uniforms (_uniform_rows) - or None with augmentation off.  Drawn FIRST in a step (before the latents)."""
+        return self._uniform_rows(images_real, augment_u, 8, self._aug_policy or self._aug_geom, "augment_u",
+                                  "augments nothing (augment / SP_AUGMENT)")
 
     def _augment_geom_rows(self, images_real, augment_v):
-        """The step's (3, B, 4) uniforms of the geometric words, rows as in _augment_rows - or None without geometric words.  Drawn right
-        behind the (3, B, 8) draw and in front of the latents unless the caller brings them."""
-        if not self._aug_geom:
-            if augment_v is not None:
-                raise ops.L.SempyrError("augment_v given, but this ModelWrapper has no geometric augmentation (xflip / rot90 / scale / rotate "
-                                        "in augment / SP_AUGMENT)")
-            return None
-        shape = (3, images_real.shape[0], 4)
-        if augment_v is None:
-            return torch.rand(shape, dtype=torch.float32, device=images_real.device)
-        if tuple(augment_v.shape) != shape:
-            raise ops.L.SempyrError("augment_v must be %s (three transforms x batch x 4 uniforms), got %s" % (shape, tuple(augment_v.shape)))
-        return augment_v.detach().to(device=images_real.device, dtype=torch.float32).contiguous()
+        """The step's (3, B, 4) uniforms of the geometric words (_uniform_rows) - or None without geometric words.  Drawn right behind the
+        (3, B, 8) draw and in front of the latents."""
+        return self._uniform_rows(images_real, augment_v, 4, self._aug_geom, "augment_v",
+                                  "has no geometric augmentation (xflip / rot90 / scale / rotate in augment / SP_AUGMENT)")
 
     def _augment_tables(self, images_real, aug_u, aug_v, out=None):
         """The step's (3, B, 8) affine tables: all 3B rows in ONE decode launch (into `out`, the graphs' static buffer, if given) - or

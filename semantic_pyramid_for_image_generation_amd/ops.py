@@ -1683,6 +1683,11 @@ def rows_to_nhwc(x, c, h, w, dest: Optional[Dest] = None):
     return _PermuteFn.apply(x, c, h, w, True, dest)
 
 
+def _float3(values):
+    """scale3 / shift3 of the plain ingest for L.call: a 3-float array behind a void pointer (which keeps it alive), or None."""
+    return None if values is None else ctypes.cast((ctypes.c_float * 3)(*values), ctypes.c_void_p)
+
+
 class _IngestFn(torch.autograd.Function):
     """3-channel image (any strides; fp32 or compute dtype) -> NHWC with zero-padded channels, optional affine."""
 
@@ -1692,12 +1697,9 @@ class _IngestFn(torch.autograd.Function):
         n, c, h, w = img.shape
         cp = pad_channels(c, dtype)
         y = nhwc_empty(n, cp, h, w, dtype, img.device)
-        sc = (ctypes.c_float * 3)(*scale3) if scale3 is not None else None
-        sf = (ctypes.c_float * 3)(*shift3) if shift3 is not None else None
         sn, scs, sh, sw = img.stride()
-        L.call("sp_ingest_image", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, ptr(y), n, c, h, w, cp,
-               ctypes.cast(sc, ctypes.c_void_p) if sc is not None else None,
-               ctypes.cast(sf, ctypes.c_void_p) if sf is not None else None, sp_dtype(dtype), stream())
+        L.call("sp_ingest_image", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, ptr(y), n, c, h, w, cp, _float3(scale3), _float3(shift3),
+               sp_dtype(dtype), stream())
         ctx.cfg = (n, c, h, w, cp, scale3, img.dtype)
         return y
 
@@ -1706,9 +1708,7 @@ class _IngestFn(torch.autograd.Function):
         n, c, h, w, cp, scale3, src_dtype = ctx.cfg
         dy = as_nhwc(dy)
         dsrc = nhwc_empty(n, c, h, w, dy.dtype, dy.device)
-        sc = (ctypes.c_float * 3)(*scale3) if scale3 is not None else None
-        L.call("sp_ingest_image_bwd", ptr(dy), cp, ptr(dsrc), c, n * h * w,
-               ctypes.cast(sc, ctypes.c_void_p) if sc is not None else None, sp_dtype(dy.dtype), stream())
+        L.call("sp_ingest_image_bwd", ptr(dy), cp, ptr(dsrc), c, n * h * w, _float3(scale3), sp_dtype(dy.dtype), stream())
         if dsrc.dtype != src_dtype:
             dsrc = dsrc.to(src_dtype)
         return dsrc, None, None, None
@@ -1729,13 +1729,11 @@ def ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, scale3=No
         cp = pad_channels(c, dtype)
         y = nhwc_empty(na + nb, cp, h, w, dtype, img_a.device)
         esz = y.element_size()
-        sc = (ctypes.c_float * 3)(*scale3) if scale3 is not None else None
-        sf = (ctypes.c_float * 3)(*shift3) if shift3 is not None else None
+        sc, sf = _float3(scale3), _float3(shift3)
         for img, off in ((img_a.detach(), 0), (img_b.detach(), na)):
             sn, scs, sh, sw = img.stride()
             L.call("sp_ingest_image", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz),
-                   img.shape[0], c, h, w, cp, ctypes.cast(sc, ctypes.c_void_p) if sc is not None else None,
-                   ctypes.cast(sf, ctypes.c_void_p) if sf is not None else None, sp_dtype(dtype), stream())
+                   img.shape[0], c, h, w, cp, sc, sf, sp_dtype(dtype), stream())
     return y
 
 
@@ -1744,26 +1742,32 @@ AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
 _AUG_WORDS = {"color": AUG_COLOR, "translation": AUG_TRANSLATION, "cutout": AUG_CUTOUT}
 
 
-def augment_policy(policy) -> int:
-    """"color,translation,cutout" (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask of
-    include/sempyr.h's SP_AUG_*.  An unknown word raises."""
-    if policy is None:
+def _word_mask(value, table, what) -> int:
+    """A comma-separated string of `table`'s words (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask.
+    what: how the errors name the family ("augmentation policy")."""
+    if value is None:
         return 0
-    if isinstance(policy, int) and not isinstance(policy, bool):
-        if not 0 <= policy <= 7:
-            raise L.SempyrError("augmentation policy mask %d: not an OR of color (1), translation (2), cutout (4)" % policy)
-        return policy
-    if not isinstance(policy, str):
-        raise L.SempyrError("augmentation policy: a comma-separated string of %s (got %r)" % (" / ".join(_AUG_WORDS), policy))
+    if isinstance(value, int) and not isinstance(value, bool):
+        if not 0 <= value <= sum(table.values()):
+            raise L.SempyrError("%s mask %d: not an OR of %s" % (what, value, ", ".join("%s (%d)" % wb for wb in table.items())))
+        return value
+    if not isinstance(value, str):
+        raise L.SempyrError("%s: a comma-separated string of %s (got %r)" % (what, " / ".join(table), value))
     mask = 0
-    for word in policy.split(","):
+    for word in value.split(","):
         word = word.strip()
         if not word:
             continue
-        if word not in _AUG_WORDS:
-            raise L.SempyrError("augmentation policy word %r: choose among %s" % (word, ", ".join(_AUG_WORDS)))
-        mask |= _AUG_WORDS[word]
+        if word not in table:
+            raise L.SempyrError("%s word %r: choose among %s" % (what, word, ", ".join(table)))
+        mask |= table[word]
     return mask
+
+
+def augment_policy(policy) -> int:
+    """"color,translation,cutout" (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask of
+    include/sempyr.h's SP_AUG_*.  An unknown word raises."""
+    return _word_mask(policy, _AUG_WORDS, "augmentation policy")
 
 
 def augment_geometry(h: int, w: int):
@@ -1807,23 +1811,7 @@ _GEOM_WORDS = {"xflip": GEOM_XFLIP, "rot90": GEOM_ROT90, "scale": GEOM_SCALE, "r
 def augment_geom(words) -> int:
     """"xflip,rot90,scale,rotate" (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask of include/sempyr.h's
     SP_GEOM_*.  An unknown word raises (the words of augment_policy included: augment_split takes both families)."""
-    if words is None:
-        return 0
-    if isinstance(words, int) and not isinstance(words, bool):
-        if not 0 <= words <= 15:
-            raise L.SempyrError("geometric augmentation mask %d: not an OR of xflip (1), rot90 (2), scale (4), rotate (8)" % words)
-        return words
-    if not isinstance(words, str):
-        raise L.SempyrError("geometric augmentation: a comma-separated string of %s (got %r)" % (" / ".join(_GEOM_WORDS), words))
-    mask = 0
-    for word in words.split(","):
-        word = word.strip()
-        if not word:
-            continue
-        if word not in _GEOM_WORDS:
-            raise L.SempyrError("geometric augmentation word %r: choose among %s" % (word, ", ".join(_GEOM_WORDS)))
-        mask |= _GEOM_WORDS[word]
-    return mask
+    return _word_mask(words, _GEOM_WORDS, "geometric augmentation")
 
 
 def augment_split(policy):
@@ -1918,18 +1906,20 @@ def _augment_args(img, u, policy):
     return policy
 
 
+def _augment_slices(entry, h, w, backward):
+    out = ctypes.c_int64(0)
+    L.call(entry, h, w, 1 if backward else 0, ctypes.byref(out))
+    return int(out.value)
+
+
 def augment_slices(h: int, w: int, backward: bool) -> int:
     """Partials per image that the statistics launch of the augmenting ingest writes (include/sempyr.h: sp_augment_slices)."""
-    out = ctypes.c_int64(0)
-    L.call("sp_augment_slices", h, w, 1 if backward else 0, ctypes.byref(out))
-    return int(out.value)
+    return _augment_slices("sp_augment_slices", h, w, backward)
 
 
 def augment_geom_slices(h: int, w: int, backward: bool) -> int:
     """Partials per image of the geometric entries' statistics launch (include/sempyr.h: sp_augment_geom_slices)."""
-    out = ctypes.c_int64(0)
-    L.call("sp_augment_geom_slices", h, w, 1 if backward else 0, ctypes.byref(out))
-    return int(out.value)
+    return _augment_slices("sp_augment_geom_slices", h, w, backward)
 
 
 def _augment_partials(n, h, w, policy, backward, device, geom=False):
@@ -1949,20 +1939,23 @@ def _augment_gate(p, device):
     return p
 
 
+def _augment_entry(backward, p, table, part):
+    """(name, arguments between `policy` and `dtype`) of the entry for this call - include/sempyr.h: the geometric entries with a table
+    (p may be NULL there), the gated ones with p alone, else the plain ones."""
+    bwd = "_bwd" if backward else ""
+    if table is not None:
+        return "sp_augment_geom_ingest" + bwd, (ptr(table), ptr(part), ptr(p))
+    if p is not None:
+        return "sp_augment_ingest%s_gated" % bwd, (ptr(part), ptr(p))
+    return "sp_augment_ingest" + bwd, (ptr(part),)
+
+
 def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None, table=None):
     n, _, h, w = img.shape
     sn, scs, sh, sw = img.stride()
     part = _augment_partials(n, h, w, policy, False, img.device, table is not None)
-    if table is not None:
-        L.call("sp_augment_geom_ingest", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(table),
-               ptr(part), ptr(p), sp_dtype(dtype), stream())
-        return
-    if p is not None:
-        L.call("sp_augment_ingest_gated", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(part),
-               ptr(p), sp_dtype(dtype), stream())
-        return
-    L.call("sp_augment_ingest", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, ptr(part),
-           sp_dtype(dtype), stream())
+    name, extra = _augment_entry(False, p, table, part)
+    L.call(name, ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, *extra, sp_dtype(dtype), stream())
 
 
 class _AugmentIngestFn(torch.autograd.Function):
@@ -1986,14 +1979,8 @@ class _AugmentIngestFn(torch.autograd.Function):
         dy = as_nhwc(dy)
         dsrc = nhwc_empty(n, 3, h, w, dy.dtype, dy.device)
         part = _augment_partials(n, h, w, policy, True, dy.device, ctx.table is not None)
-        if ctx.table is not None:
-            L.call("sp_augment_geom_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(ctx.table), ptr(part), ptr(ctx.p),
-                   sp_dtype(dy.dtype), stream())
-        elif ctx.p is not None:
-            L.call("sp_augment_ingest_bwd_gated", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), ptr(ctx.p),
-                   sp_dtype(dy.dtype), stream())
-        else:
-            L.call("sp_augment_ingest_bwd", ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, ptr(part), sp_dtype(dy.dtype), stream())
+        name, extra = _augment_entry(True, ctx.p, ctx.table, part)
+        L.call(name, ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, *extra, sp_dtype(dy.dtype), stream())
         if dsrc.dtype != src_dtype:
             dsrc = dsrc.to(src_dtype)
         return dsrc, None, None, None, None, None
