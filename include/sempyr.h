@@ -607,6 +607,55 @@ int sp_augment_geom_ingest(const void* src, int32_t src_dtype, int64_t sn, int64
 int sp_augment_geom_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                int32_t policy, const float* table, float* partials, const float* p_dev, int32_t dtype,
                                sp_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
+ * ADA's color group inside the ingest pass (Karras et al. 2020, "ADA": brightness, contrast, luma flip, hue rotation, saturation): ONE
+ * affine map of RGB per image, a 3 x 4 matrix.  No reduction and no launch besides one decode per step; the backward is the transposed
+ * 3 x 3 matrix.  The reference has NO counterpart.  DESIGN.md section 20.
+ *
+ * Images are 3-channel, valued as the generator emits them (contrast and luma flip act about 0); fp32 arithmetic whatever the storage
+ * type.  One application takes the image's rows u and v with their meaning unchanged, a row z of 8 fp32 uniforms in [0, 1) and `cmat`,
+ * any OR of SP_CMAT_*; a part that is left out is the identity and is not computed.
+ * Decode (fp32, every product and sum rounded once), with nrm(a, b) = sqrtf(-2 * logf(1 - a)) * cosf(float(2 pi) * b) (Box-Muller;
+ * 1 - a >= 2^-24, so |nrm| <= 5.77):
+ *   brightness  bb = 0.2f * nrm(z0, z1)                                                   left out: 0
+ *   contrast    c  = exp2f(0.5f * nrm(z2, z3))                                            left out: 1
+ *   saturation  s  = exp2f(nrm(z4, z5))                                                   left out: 1
+ *   hue         theta = (2 z6 - 1) * float(pi), cs = cosf(theta), sn = sinf(theta)        left out: cs = 1, sn = 0 exactly
+ *   luma flip   f  = z7 < 0.5f ? -1 : 1                                                   left out: 1
+ * With P = J / 3 the projector on the grey axis (1, 1, 1) / sqrt 3, Q = I - P and K the cross-product matrix of that axis, ADA's five
+ * homogeneous matrices in its order (brightness, contrast, luma flip, hue, saturation, each multiplied on the left) collapse to
+ *   out = Lm x + t (1, 1, 1),   Lm = c (f P + s cos(theta) Q + s sin(theta) K),   t = c f bb
+ * evaluated as  p = c f;  cs_ = c s;  beta = cs_ cs;  gamma = (cs_ sn) float(1 / sqrt 3);  d = (p - beta) / 3;
+ *   Lm_ii = beta + d;  Lm_01 = Lm_12 = Lm_20 = d - gamma;  Lm_02 = Lm_10 = Lm_21 = d + gamma;  t = p bb.
+ * (float(1 / sqrt 3) is the kernel's fp32 rounding of the closed form's constant 1 / sqrt 3, a rounding like any other of the decode:
+ * a float64 reference of Lm uses 1 / sqrt 3 itself, which differs by 3e-8 relative in gamma.)
+ * A row with brightness and / or contrast alone is exactly diag(c) with offset c bb; luma flip alone is I - 2 J / 3 to rounding.
+ * Table row (the "ctable"): 12 floats {L00, L01, L02, t, L10, L11, L12, t, L20, L21, L22, t}: three 16-byte quadruples, row-major.
+ * Forward: the last step of the pointwise color stage e of the SOURCE pixel - after `color` above when that is on too, before
+ * translation / resampling / cutout:  e'_r = ((L_r0 e_0 + L_r1 e_1) + L_r2 e_2) + L_r3  (the kernel may contract into FMAs).  In the
+ * geometric family it is evaluated at each tap, so a tap outside the frame still contributes 0 and the window still zeroes its outputs.
+ * Backward: after the family's g1,  g1'_c = (L_0c g1_0 + L_1c g1_1) + L_2c g1_2,  then the color backward unchanged on g1'.  Its
+ * statistics launch takes sum(g1') per output pixel as (k0 dy_0 + k1 dy_1) + k2 dy_2, k_r = (L_r0 + L_r1) + L_r2, times the in-frame tap
+ * weights in the geometric family.  Without SP_AUG_COLOR there is no statistics launch in either direction.  The gate is unchanged.
+ *
+ * sp_augment_cmat_decode      ONE tiny launch: n x 12 floats into `ctable` from z (n x 8).  cmat in 1 ... 31 and n in 1 ... 2^24, else
+ *                             refused.
+ * sp_augment_cmat_ingest      `table` NULL: stands where sp_augment_ingest_gated stands (the plain family); non-NULL: where
+ * sp_augment_cmat_ingest_bwd  sp_augment_geom_ingest stands.  p_dev NULL: every image is live.  ANY 3 x 4 ctable is admitted, not only
+ *                             decoded ones.  `partials` is sized by sp_augment_slices / sp_augment_geom_slices as before.
+ * `ctable` must be 16-byte aligned in all three entries (a row is read and written as three 16-byte quadruples; a row's pitch of 48
+ * bytes keeps every row aligned).
+ * Refusals launch nothing: NULL z / ctable, a ctable that is not 16-byte aligned, a bad cmat, n <= 0 (decode: n > 2^24), and everything
+ * the entries above refuse.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SP_CMAT_BRIGHTNESS = 1, SP_CMAT_CONTRAST = 2, SP_CMAT_LUMAFLIP = 4, SP_CMAT_HUE = 8, SP_CMAT_SATURATION = 16 };
+int sp_augment_cmat_decode(const float* z, int32_t n, int32_t cmat, float* ctable, sp_stream_t stream);
+int sp_augment_cmat_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                           int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, const float* table,
+                           const float* ctable, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream);
+int sp_augment_cmat_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                               int32_t policy, const float* table, const float* ctable, float* partials, const float* p_dev,
+                               int32_t dtype, sp_stream_t stream);
 int sp_mask_concat(const void* feat, const float* mask, void* out, int64_t pixels, int32_t c, int32_t cp,
                    int32_t dtype, sp_stream_t stream);
 int sp_mask_mul_2d(const void* feat, int32_t ldf, const float* mask, void* out, int32_t ldo, int32_t batch,

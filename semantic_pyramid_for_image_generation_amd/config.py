@@ -37,7 +37,8 @@ results beyond floating-point summation order.  The kernel library itself reads 
                                                           keeps, evaluates (validate / inference) and saves; 0 = off: no launch, no allocation, no checkpoint key
     augment               SP_AUGMENT             ""       differentiable augmentation of every image the discriminator sees, inside its ingest pass (csrc/augment.hip,
                                                           DESIGN.md 11): a comma-separated subset of color, translation, cutout and of the geometric words
-                                                          xflip, rot90, scale, rotate; empty = off: no draw, no launch,
+                                                          xflip, rot90, scale, rotate and of ADA's color words brightness, contrast, lumaflip,
+                                                          hue, saturation (one 3 x 4 matrix per image); empty = off: no draw, no launch,
                                                           no allocation (the one switch here that DOES change results: it is part of the training recipe)
     augment_p             SP_AUGMENT_P           ""       with augment only: the probability with which each image is transformed (csrc/augment.hip: the gate,
                                                           DESIGN.md 15) - a number in [0, 1] = fixed; "adaptive" or "adaptive:<target>" = steered on the device from

@@ -59,6 +59,33 @@
 // tiles (geom_tile_pixel), four taps x three channels from the strided source (a block's footprint is a patch of some 30 x 30 pixels
 // that stays in L2; no LDS staging), one 16-byte padded store; backward - one source pixel per thread in the same tiles, up to 25
 // 16-byte loads of padded dy pixels, L^-1 once per block.
+//
+// THE COLOR MATRIX (Karras et al. 2020: ADA's color group - brightness, contrast, luma flip, hue rotation, saturation; DESIGN.md section
+// 20; include/sempyr.h repeats it).  ONE affine map of RGB per image: no reduction, no launch besides one decode per step, and the
+// backward is the transposed 3 x 3 matrix.  Images are valued as the generator emits them (contrast and luma flip act about 0).  A row z
+// of 8 fp32 uniforms in [0, 1) joins u and v; cmat = any OR of SP_CMAT_BRIGHTNESS 1 / CONTRAST 2 / LUMAFLIP 4 / HUE 8 / SATURATION 16, a
+// part left out is the identity and is not computed.  Decode (fp32, every product and sum rounded once), with
+//   nrm(a, b) = sqrtf(-2 * logf(1 - a)) * cosf(float(2 pi) * b)      (Box-Muller; 1 - a >= 2^-24, so |nrm| <= 5.77):
+//   bb = 0.2f nrm(z0, z1) (else 0);  c = exp2f(0.5f nrm(z2, z3)) (else 1);  s = exp2f(nrm(z4, z5)) (else 1);
+//   theta = (2 z6 - 1) float(pi), cs = cosf(theta), sn = sinf(theta) (else cs = 1, sn = 0 exactly);  f = z7 < 0.5f ? -1 : 1 (else 1).
+// With P = J / 3 the projector on the grey axis (1, 1, 1) / sqrt 3, Q = I - P and K the cross-product matrix of that axis, ADA's five
+// homogeneous matrices in its order (brightness, contrast, luma flip, hue as Rodrigues' rotation about the grey axis, saturation, each
+// multiplied on the left) collapse to  out = Lm x + t (1, 1, 1),  Lm = c (f P + s cos(theta) Q + s sin(theta) K),  t = c f bb:
+//   p = c f;  cs_ = c s;  beta = cs_ cs;  gamma = (cs_ sn) float(1 / sqrt 3);  d = (p - beta) / 3;
+//   Lm_ii = beta + d;  Lm_01 = Lm_12 = Lm_20 = d - gamma;  Lm_02 = Lm_10 = Lm_21 = d + gamma;  t = p bb.
+// Brightness and / or contrast alone is exactly diag(c) with offset c bb; luma flip alone is I - 2 J / 3 to rounding.
+// Table row (the "ctable"): 12 floats {L00, L01, L02, t, L10, L11, L12, t, L20, L21, L22, t} - three 16-byte quadruples, row-major.
+// Forward: the last step of the pointwise color stage e of the SOURCE pixel (after `color`, before translation / resampling / cutout):
+//   e'_r = ((L_r0 e_0 + L_r1 e_1) + L_r2 e_2) + L_r3      (the compiler may contract it into FMAs)
+// In the geometric family it is evaluated at each tap, as aug_color_fwd is: a tap outside the frame still contributes 0.  The apply
+// entries take ANY 3 x 4 table.  Backward: after the family's g1,  g1'_c = (L_0c g1_0 + L_1c g1_1) + L_2c g1_2,  then the color backward
+// unchanged on g1'.  Its statistics launch needs sum(g1') before g1 exists: per output pixel (k0 dy_0 + k1 dy_1) + k2 dy_2 with
+// k_r = (L_r0 + L_r1) + L_r2, times the in-frame tap weights in the geometric family.  Without `color` the matrix adds no statistics
+// launch in either direction.  The gate is unchanged: a dead image never reads its ctable row.
+// LAUNCHES: cmat_decode_kernel - one thread per row, n x 12 floats; the apply and backward statistics kernels take `ctable`, NULL for the
+// entries above (their bits are unchanged); with a table each block reads its image's 12 floats once as three 16-byte loads from a
+// block-uniform address (wave-uniform: the compiler turns them into scalar loads, one of 32 and one of 16 bytes).  ctable must be 16-byte
+// aligned.  float(1 / sqrt 3) above is the fp32 rounding of the closed form's constant; a float64 reference uses 1 / sqrt 3 itself.
 #include "common.h"
 
 namespace {
@@ -167,6 +194,42 @@ __device__ __forceinline__ void aug_color_fwd(float (&e)[3], const AugImage& a, 
     }
 }
 
+// the color matrix of one image (header comment: THE COLOR MATRIX): three rows {L_r0, L_r1, L_r2, t}
+struct CMat { float4 r[3]; };
+
+// block-uniform address: three 16-byte loads per block.  ctable == NULL (the entries without one): never applied, nothing is read.
+__device__ __forceinline__ CMat cmat_load(const float* __restrict__ ctable, int n) {
+    CMat m;
+    if (ctable != nullptr) {
+        const float4* t = reinterpret_cast<const float4*>(ctable + (long)n * 12);
+        m.r[0] = t[0]; m.r[1] = t[1]; m.r[2] = t[2];
+    } else {
+        m.r[0] = make_float4(1.f, 0.f, 0.f, 0.f); m.r[1] = make_float4(0.f, 1.f, 0.f, 0.f); m.r[2] = make_float4(0.f, 0.f, 1.f, 0.f);
+    }
+    return m;
+}
+
+// e'_r = ((L_r0 e_0 + L_r1 e_1) + L_r2 e_2) + L_r3: the last step of a source pixel's color stage
+__device__ __forceinline__ void cmat_fwd(float (&e)[3], const CMat& m) {
+    const float e0 = e[0], e1 = e[1], e2 = e[2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = ((m.r[r].x * e0 + m.r[r].y * e1) + m.r[r].z * e2) + m.r[r].w;
+}
+
+// g1'_c = (L_0c g1_0 + L_1c g1_1) + L_2c g1_2: the transposed 3 x 3 matrix, in front of the color backward
+__device__ __forceinline__ void cmat_bwd(float (&v)[3], const CMat& m) {
+    const float g0 = v[0], g1 = v[1], g2 = v[2];
+    v[0] = (m.r[0].x * g0 + m.r[1].x * g1) + m.r[2].x * g2;
+    v[1] = (m.r[0].y * g0 + m.r[1].y * g1) + m.r[2].y * g2;
+    v[2] = (m.r[0].z * g0 + m.r[1].z * g1) + m.r[2].z * g2;
+}
+
+// sum_c g1'_c of one output pixel's dy: (k0 dy_0 + k1 dy_1) + k2 dy_2, k_r = (L_r0 + L_r1) + L_r2
+__device__ __forceinline__ float cmat_bwd_sum(const float (&v)[3], const CMat& m) {
+    const float k0 = (m.r[0].x + m.r[0].y) + m.r[0].z, k1 = (m.r[1].x + m.r[1].y) + m.r[1].z, k2 = (m.r[2].x + m.r[2].y) + m.r[2].z;
+    return (k0 * v[0] + k1 * v[1]) + k2 * v[2];
+}
+
 // ---- statistics, forward: partial sums of the raw source --------------------------------------------
 // dense: the image's 3 H W elements are one contiguous, 16-byte aligned run (NCHW-contiguous or channels-last): 16-byte loads.
 template <typename TS>
@@ -208,13 +271,14 @@ __global__ __launch_bounds__(256) void aug_stats_fwd_kernel(const TS* __restrict
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw,
                                                             TD* __restrict__ dst, AugGeom g, int CP, const float* __restrict__ u,
-                                                            int policy, const float* __restrict__ partials, int nsl,
-                                                            const float* __restrict__ p_dev) {
+                                                            int policy, const float* __restrict__ ctable,
+                                                            const float* __restrict__ partials, int nsl, const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
     if (!aug_gate(u, p_dev, n)) { aug_dead_fwd(src, sn, sc, sh, sw, dst, g, CP, n); return; }
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
-    const bool color = (policy & SP_AUG_COLOR) != 0;
+    const CMat cm = cmat_load(ctable, n);
+    const bool color = (policy & SP_AUG_COLOR) != 0, cmat = ctable != nullptr;
     float M = 0.f;
     if (color) M = aug_total(partials, n, nsl) / (float)(3 * HW) + a.o;
     for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
@@ -225,6 +289,7 @@ __global__ __launch_bounds__(256) void aug_apply_fwd_kernel(const TS* __restrict
 #pragma unroll
             for (int c = 0; c < 3; ++c) e[c] = Elem<TS>::ld(s + c * sc);
             if (color) aug_color_fwd(e, a, M);
+            if (cmat) cmat_fwd(e, cm);
         }
         aug_st_padded(dst + ((long)n * HW + p) * CP, CP, e);
     }
@@ -275,11 +340,14 @@ __device__ __forceinline__ void aug_color_bwd(float (&v)[3], const AugImage& a, 
 // ---- statistics, backward: partial sums of g1 = the dy values that reach an input pixel --------------
 template <typename T>
 __global__ __launch_bounds__(256) void aug_stats_bwd_kernel(const T* __restrict__ dy, int CP, AugGeom g, const float* __restrict__ u,
-                                                            int policy, float* __restrict__ partials, const float* __restrict__ p_dev) {
+                                                            int policy, const float* __restrict__ ctable, float* __restrict__ partials,
+                                                            const float* __restrict__ p_dev) {
     __shared__ float red[4];
     const int n = blockIdx.y;
     if (!aug_gate(u, p_dev, n)) return;      // a dead image: nobody reads its partials (block-uniform)
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
+    const CMat cm = cmat_load(ctable, n);
+    const bool cmat = ctable != nullptr;
     const int HW = g.H * g.W;
     const int beg = blockIdx.x * AUG_BWD_SLICE;
     const int end = beg + AUG_BWD_SLICE < HW ? beg + AUG_BWD_SLICE : HW;
@@ -289,7 +357,7 @@ __global__ __launch_bounds__(256) void aug_stats_bwd_kernel(const T* __restrict_
         if (aug_live(a, g, h, w)) {
             float v[3];
             aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
-            acc += (v[0] + v[1]) + v[2];
+            acc += cmat ? cmat_bwd_sum(v, cm) : (v[0] + v[1]) + v[2];
         }
     }
     acc = block_sum_256(acc, red);
@@ -299,13 +367,14 @@ __global__ __launch_bounds__(256) void aug_stats_bwd_kernel(const T* __restrict_
 // ---- apply, backward: padded dy -> NHWC gradient of pitch 3 (what ingest_bwd_kernel writes) ------------
 template <typename T>
 __global__ __launch_bounds__(256) void aug_apply_bwd_kernel(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, AugGeom g,
-                                                            const float* __restrict__ u, int policy, const float* __restrict__ partials,
-                                                            int nsl, const float* __restrict__ p_dev) {
+                                                            const float* __restrict__ u, int policy, const float* __restrict__ ctable,
+                                                            const float* __restrict__ partials, int nsl, const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
     if (!aug_gate(u, p_dev, n)) { aug_dead_bwd(dy, CP, dsrc, g, n); return; }
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
-    const bool color = (policy & SP_AUG_COLOR) != 0;
+    const CMat cm = cmat_load(ctable, n);
+    const bool color = (policy & SP_AUG_COLOR) != 0, cmat = ctable != nullptr;
     float Gm = 0.f;
     if (color) Gm = aug_total(partials, n, nsl) / (float)(3 * HW);
     for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
@@ -314,6 +383,7 @@ __global__ __launch_bounds__(256) void aug_apply_bwd_kernel(const T* __restrict_
         float v[3] = {0.f, 0.f, 0.f};
         if (ho >= 0 && ho < g.H && wo >= 0 && wo < g.W && !aug_in_window(a, ho, wo))
             aug_ld3(dy + ((long)n * HW + (long)ho * g.W + wo) * CP, CP, v);
+        if (cmat) cmat_bwd(v, cm);
         if (color) aug_color_bwd(v, a, Gm);
         aug_st3(dsrc + ((long)n * HW + p) * 3, v);
     }
@@ -410,7 +480,7 @@ __global__ __launch_bounds__(64) void geom_decode_kernel(const float* __restrict
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw,
                                                              TD* __restrict__ dst, AugGeom g, int CP, const float* __restrict__ u,
-                                                             int policy, const float* __restrict__ table,
+                                                             int policy, const float* __restrict__ table, const float* __restrict__ ctable,
                                                              const float* __restrict__ partials, int nsl, const float* __restrict__ p_dev) {
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
@@ -418,7 +488,8 @@ __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restric
     if (!aug_gate(u, p_dev, n)) { aug_dead_fwd(src, sn, sc, sh, sw, dst, g, CP, n); return; }
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);          // color and cutout only: the entry masks the translation out
     const GeomMap m = geom_map(table, n);
-    const bool color = (policy & SP_AUG_COLOR) != 0;
+    const CMat cm = cmat_load(ctable, n);
+    const bool color = (policy & SP_AUG_COLOR) != 0, cmat = ctable != nullptr;
     float M = 0.f;
     if (color) M = aug_total(partials, n, nsl) / (float)(3 * HW) + a.o;
     const int tiles_w = (g.W + 15) >> 4, tiles = ((g.H + 15) >> 4) * tiles_w;
@@ -442,6 +513,7 @@ __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restric
 #pragma unroll
                         for (int c = 0; c < 3; ++c) t[r][q][c] = Elem<TS>::ld(s + c * sc);
                         if (color) aug_color_fwd(t[r][q], a, M);
+                        if (cmat) cmat_fwd(t[r][q], cm);
                     }
                 }
             }
@@ -456,13 +528,15 @@ __global__ __launch_bounds__(256) void geom_apply_fwd_kernel(const TS* __restric
 // ---- statistics, backward: sum(g1) taken over OUTPUT pixels: (dy_0 + dy_1 + dy_2) x (sum of the in-frame tap weights) ----------------
 template <typename T>
 __global__ __launch_bounds__(256) void geom_stats_bwd_kernel(const T* __restrict__ dy, int CP, AugGeom g, const float* __restrict__ u,
-                                                             int policy, const float* __restrict__ table, float* __restrict__ partials,
-                                                             const float* __restrict__ p_dev) {
+                                                             int policy, const float* __restrict__ table, const float* __restrict__ ctable,
+                                                             float* __restrict__ partials, const float* __restrict__ p_dev) {
     __shared__ float red[4];
     const int n = blockIdx.y;
     if (!aug_gate(u, p_dev, n)) return;      // a dead image: nobody reads its partials (block-uniform)
     const AugImage a = aug_decode(u + (long)n * 8, policy, g);
     const GeomMap m = geom_map(table, n);
+    const CMat cm = cmat_load(ctable, n);
+    const bool cmat = ctable != nullptr;
     const int HW = g.H * g.W;
     const int beg = blockIdx.x * AUG_BWD_SLICE;
     const int end = beg + AUG_BWD_SLICE < HW ? beg + AUG_BWD_SLICE : HW;
@@ -478,7 +552,7 @@ __global__ __launch_bounds__(256) void geom_stats_bwd_kernel(const T* __restrict
             const float wx = (ax.in0 ? ax.w0 : 0.f) + (ax.in1 ? ax.w1 : 0.f);
             float v[3];
             aug_ld3(dy + ((long)n * HW + p) * CP, CP, v);
-            acc += ((v[0] + v[1]) + v[2]) * (wy * wx);
+            acc += (cmat ? cmat_bwd_sum(v, cm) : (v[0] + v[1]) + v[2]) * (wy * wx);
         }
     }
     acc = block_sum_256(acc, red);
@@ -490,7 +564,8 @@ __global__ __launch_bounds__(256) void geom_stats_bwd_kernel(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void geom_apply_bwd_kernel(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, AugGeom g,
                                                              const float* __restrict__ u, int policy, const float* __restrict__ table,
-                                                             const float* __restrict__ partials, int nsl, const float* __restrict__ p_dev) {
+                                                             const float* __restrict__ ctable, const float* __restrict__ partials, int nsl,
+                                                             const float* __restrict__ p_dev) {
     __shared__ float inv[4];
     const int n = blockIdx.y;
     const int HW = g.H * g.W;
@@ -502,7 +577,8 @@ __global__ __launch_bounds__(256) void geom_apply_bwd_kernel(const T* __restrict
         inv[0] = m.m11 * r; inv[1] = -m.m01 * r; inv[2] = -m.m10 * r; inv[3] = m.m00 * r;
     }
     __syncthreads();
-    const bool color = (policy & SP_AUG_COLOR) != 0;
+    const CMat cm = cmat_load(ctable, n);
+    const bool color = (policy & SP_AUG_COLOR) != 0, cmat = ctable != nullptr;
     float Gm = 0.f;
     if (color) Gm = aug_total(partials, n, nsl) / (float)(3 * HW);
     const int tiles_w = (g.W + 15) >> 4, tiles = ((g.H + 15) >> 4) * tiles_w;
@@ -539,9 +615,40 @@ __global__ __launch_bounds__(256) void geom_apply_bwd_kernel(const T* __restrict
                 for (int c = 0; c < 3; ++c) v[c] += wgt * d[c];
             }
         }
+        if (cmat) cmat_bwd(v, cm);
         if (color) aug_color_bwd(v, a, Gm);
         aug_st3(dsrc + ((long)n * HW + p) * 3, v);
     }
+}
+
+// ---- the color matrix's decode: one thread per row of z, n x 12 floats (header comment: THE COLOR MATRIX) -----------------------------
+// Box-Muller: |nrm| <= sqrt(-2 log 2^-24) = 5.77
+__device__ __forceinline__ float cmat_nrm(float a, float b) {
+    return __fmul_rn(__fsqrt_rn(__fmul_rn(-2.f, logf(__fsub_rn(1.f, a)))), cosf(__fmul_rn(6.28318530717958647692f, b)));
+}
+
+__global__ __launch_bounds__(64) void cmat_decode_kernel(const float* __restrict__ z, int n, int cmat, float* __restrict__ ctable) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float* zi = z + (long)i * 8;
+    float bb = 0.f, c = 1.f, s = 1.f, cs = 1.f, sn = 0.f, f = 1.f;
+    if (cmat & SP_CMAT_BRIGHTNESS) bb = __fmul_rn(0.2f, cmat_nrm(zi[0], zi[1]));
+    if (cmat & SP_CMAT_CONTRAST) c = exp2f(__fmul_rn(0.5f, cmat_nrm(zi[2], zi[3])));
+    if (cmat & SP_CMAT_SATURATION) s = exp2f(cmat_nrm(zi[4], zi[5]));
+    if (cmat & SP_CMAT_HUE) {
+        const float theta = __fmul_rn(__fsub_rn(__fmul_rn(2.f, zi[6]), 1.f), 3.14159265358979323846f);
+        cs = cosf(theta);
+        sn = sinf(theta);
+    }
+    if ((cmat & SP_CMAT_LUMAFLIP) && zi[7] < 0.5f) f = -1.f;
+    const float p = __fmul_rn(c, f), cs_ = __fmul_rn(c, s);
+    const float beta = __fmul_rn(cs_, cs), gamma = __fmul_rn(__fmul_rn(cs_, sn), 0.57735026918962576451f);
+    const float d = __fdiv_rn(__fsub_rn(p, beta), 3.f);
+    const float di = __fadd_rn(beta, d), lo = __fsub_rn(d, gamma), hi = __fadd_rn(d, gamma), t = __fmul_rn(p, bb);
+    float4* row = reinterpret_cast<float4*>(ctable + (long)i * 12);
+    row[0] = make_float4(di, lo, hi, t);
+    row[1] = make_float4(hi, di, lo, t);
+    row[2] = make_float4(lo, hi, di, t);
 }
 
 inline int geom_apply_blocks(int h, int w) {          // one block per 16 x 16 tile, AUG_APPLY_BLOCKS at most (the kernels stride beyond)
@@ -551,14 +658,15 @@ inline int geom_apply_blocks(int h, int w) {          // one block per 16 x 16 t
 
 // ---- the host side: ONE checked call path for the three entry families (plain, gated, geometric) ----------------------------------------
 // What an extern "C" entry was given.  Forward: src -> dst with the source's strides.  Backward: src = dy, dst = dsrc, src_dtype = dtype,
-// no strides.  geom: a geometric entry, which resamples through `table`; p_dev NULL: every image is live.
+// no strides.  geom: a geometric entry, which resamples through `table`; ctable: NULL, or the color matrices of the sp_augment_cmat_*
+// entries (which then also choose the family: geom = table non-NULL); p_dev NULL: every image is live.
 struct AugCall {
     const char* name;
     const void* src; int32_t src_dtype; int64_t sn, sc, sh, sw;
     void* dst;
     int32_t n, h, w, cp;
     const float* u; int32_t policy;
-    bool geom; const float* table;
+    bool geom; const float* table; const float* ctable;
     float* partials; const float* p_dev;
     int32_t dtype; sp_stream_t stream;
 };
@@ -577,10 +685,10 @@ void aug_launch_fwd(const AugCall& c, const AugGeom& g) {
     }
     if (c.geom) {
         hipLaunchKernelGGL((geom_apply_fwd_kernel<TS, TD>), dim3(geom_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, src, c.sn, c.sc, c.sh, c.sw,
-                           (TD*)c.dst, g, c.cp, c.u, c.policy, c.table, c.partials, nsl, c.p_dev);
+                           (TD*)c.dst, g, c.cp, c.u, c.policy, c.table, c.ctable, c.partials, nsl, c.p_dev);
     } else {
         hipLaunchKernelGGL((aug_apply_fwd_kernel<TS, TD>), dim3(aug_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, src, c.sn, c.sc, c.sh, c.sw,
-                           (TD*)c.dst, g, c.cp, c.u, c.policy, c.partials, nsl, c.p_dev);
+                           (TD*)c.dst, g, c.cp, c.u, c.policy, c.ctable, c.partials, nsl, c.p_dev);
     }
 }
 
@@ -593,17 +701,17 @@ void aug_launch_bwd(const AugCall& c, const AugGeom& g) {
     if (c.policy & SP_AUG_COLOR) {
         nsl = aug_slices(g.H, g.W, true);
         if (c.geom) {
-            hipLaunchKernelGGL(geom_stats_bwd_kernel<T>, dim3(nsl, c.n), dim3(256), 0, s, dy, c.cp, g, c.u, c.policy, c.table, c.partials, c.p_dev);
+            hipLaunchKernelGGL(geom_stats_bwd_kernel<T>, dim3(nsl, c.n), dim3(256), 0, s, dy, c.cp, g, c.u, c.policy, c.table, c.ctable, c.partials, c.p_dev);
         } else {
-            hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, c.n), dim3(256), 0, s, dy, c.cp, g, c.u, c.policy, c.partials, c.p_dev);
+            hipLaunchKernelGGL(aug_stats_bwd_kernel<T>, dim3(nsl, c.n), dim3(256), 0, s, dy, c.cp, g, c.u, c.policy, c.ctable, c.partials, c.p_dev);
         }
     }
     if (c.geom) {
         hipLaunchKernelGGL(geom_apply_bwd_kernel<T>, dim3(geom_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, dy, c.cp, (T*)c.dst, g, c.u, c.policy,
-                           c.table, c.partials, nsl, c.p_dev);
+                           c.table, c.ctable, c.partials, nsl, c.p_dev);
     } else {
         hipLaunchKernelGGL(aug_apply_bwd_kernel<T>, dim3(aug_apply_blocks(g.H, g.W), c.n), dim3(256), 0, s, dy, c.cp, (T*)c.dst, g, c.u, c.policy,
-                           c.partials, nsl, c.p_dev);
+                           c.ctable, c.partials, nsl, c.p_dev);
     }
 }
 
@@ -709,25 +817,25 @@ extern "C" int sp_augment_geom_slices(int32_t h, int32_t w_, int32_t backward, i
 extern "C" int sp_augment_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                  int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
                                  int32_t dtype, sp_stream_t stream) {
-    return aug_run({"sp_augment_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, false, nullptr, partials, nullptr, dtype, stream}, false);
+    return aug_run({"sp_augment_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, false, nullptr, nullptr, partials, nullptr, dtype, stream}, false);
 }
 
 extern "C" int sp_augment_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                      int32_t policy, float* partials, int32_t dtype, sp_stream_t stream) {
-    return aug_run({"sp_augment_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, false, nullptr, partials, nullptr, dtype, stream}, true);
+    return aug_run({"sp_augment_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, false, nullptr, nullptr, partials, nullptr, dtype, stream}, true);
 }
 
 extern "C" int sp_augment_ingest_gated(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                        int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, float* partials,
                                        const float* p_dev, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(p_dev, "sp_augment_ingest_gated: p_dev is NULL (the ungated entry is sp_augment_ingest)");
-    return aug_run({"sp_augment_ingest_gated", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, false, nullptr, partials, p_dev, dtype, stream}, false);
+    return aug_run({"sp_augment_ingest_gated", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, false, nullptr, nullptr, partials, p_dev, dtype, stream}, false);
 }
 
 extern "C" int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                            int32_t policy, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(p_dev, "sp_augment_ingest_bwd_gated: p_dev is NULL (the ungated entry is sp_augment_ingest_bwd)");
-    return aug_run({"sp_augment_ingest_bwd_gated", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, false, nullptr, partials, p_dev, dtype, stream}, true);
+    return aug_run({"sp_augment_ingest_bwd_gated", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, false, nullptr, nullptr, partials, p_dev, dtype, stream}, true);
 }
 
 extern "C" int sp_augment_geom_decode(const float* u, const float* v, int32_t n, int32_t h, int32_t w_, int32_t policy, int32_t geom,
@@ -746,13 +854,38 @@ extern "C" int sp_augment_geom_decode(const float* u, const float* v, int32_t n,
 extern "C" int sp_augment_geom_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                       int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, const float* table,
                                       float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
-    return aug_run({"sp_augment_geom_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, true, table, partials, p_dev, dtype, stream}, false);
+    return aug_run({"sp_augment_geom_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, true, table, nullptr, partials, p_dev, dtype, stream}, false);
 }
 
 extern "C" int sp_augment_geom_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
                                           int32_t policy, const float* table, float* partials, const float* p_dev, int32_t dtype,
                                           sp_stream_t stream) {
-    return aug_run({"sp_augment_geom_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, true, table, partials, p_dev, dtype, stream}, true);
+    return aug_run({"sp_augment_geom_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, true, table, nullptr, partials, p_dev, dtype, stream}, true);
+}
+
+extern "C" int sp_augment_cmat_decode(const float* z, int32_t n, int32_t cmat, float* ctable, sp_stream_t stream) {
+    SP_CHECK_ARG(z && ctable && reinterpret_cast<uintptr_t>(ctable) % 16 == 0, "sp_augment_cmat_decode: bad args (z, ctable non-NULL, ctable 16-byte aligned)");
+    SP_CHECK_ARG(n >= 1 && n <= (1 << 24), "sp_augment_cmat_decode: n=%d (need 1 ... 2^24)", n);
+    SP_CHECK_ARG(cmat >= 1 && cmat <= 31, "sp_augment_cmat_decode: bad cmat %d (an OR of brightness 1, contrast 2, lumaflip 4, hue 8, saturation 16)", cmat);
+    hipLaunchKernelGGL(cmat_decode_kernel, dim3(sp_div_up((long)n, 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), z, n, cmat, ctable);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_augment_cmat_ingest(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
+                                      int32_t n, int32_t h, int32_t w_, int32_t cp, const float* u, int32_t policy, const float* table,
+                                      const float* ctable, float* partials, const float* p_dev, int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(ctable && reinterpret_cast<uintptr_t>(ctable) % 16 == 0, "sp_augment_cmat_ingest: ctable is NULL or not 16-byte aligned");
+    return aug_run({"sp_augment_cmat_ingest", src, src_dtype, sn, sc, sh, sw, dst, n, h, w_, cp, u, policy, table != nullptr, table, ctable, partials, p_dev,
+                    dtype, stream}, false);
+}
+
+extern "C" int sp_augment_cmat_ingest_bwd(const void* dy, int32_t cp, void* dsrc, int32_t n, int32_t h, int32_t w_, const float* u,
+                                          int32_t policy, const float* table, const float* ctable, float* partials, const float* p_dev,
+                                          int32_t dtype, sp_stream_t stream) {
+    SP_CHECK_ARG(ctable && reinterpret_cast<uintptr_t>(ctable) % 16 == 0, "sp_augment_cmat_ingest_bwd: ctable is NULL or not 16-byte aligned");
+    return aug_run({"sp_augment_cmat_ingest_bwd", dy, dtype, 0, 0, 0, 0, dsrc, n, h, w_, cp, u, policy, table != nullptr, table, ctable, partials, p_dev,
+                    dtype, stream}, true);
 }
 
 extern "C" int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream) {

@@ -22,6 +22,9 @@ sees, applied inside its ingest pass (csrc/augment.hip): t
 The words xflip, rot90, scale and rotate in the same string add the geometric family: the transforms compose with
 the translation into one affine map per image, resampled bilinearly in the same pass; a step then also draws (3, B, 4) uniforms right
 behind the first draw and decodes all 3B maps with one launch.  Without those words: no draw, no launch, no allocation, as before.
+The words brightness, contrast, lumaflip, hue and saturation add ADA's color group: one 3 x 4 matrix per image,
+applied to every source pixel as the last step of the color stage in the same pass; a step then draws one more (3, B, 8) tensor of
+uniforms behind the others and decodes all 3B matrices with one launch.  Without those words: no draw, no launch, no allocation either.
 And ``clip_grad_norm`` (or SP_CLIP_GRAD_NORM): each network's gradients are clipped by their global norm in front of its optimizer
 step - one norm for D's step, one for G's - and a step whose norm is not finite is skipped, in every storage mode, on the device
 (optim.Adam(max_grad_norm=...)); the two norms join the step's results and the log.  ``inf`` monitors and guards
@@ -138,13 +141,15 @@ class ModelWrapper(object):
         if augment is None:
             augment = CFG.augment
         # _aug_geom: the geometric words of the same string (ops.augment_split; 0: the wrapper is exactly what it is without them).
-        self._aug_policy, self._aug_geom = ops.augment_split(augment)
-        if self._aug_policy or self._aug_geom:
+        # _aug_cmat: ADA's color words of the same string (ops.augment_split3; 0: likewise).
+        self._aug_policy, self._aug_geom, self._aug_cmat = ops.augment_split3(augment)
+        if self._aug_policy or self._aug_geom or self._aug_cmat:
             if not isinstance(self.discriminator, Discriminator):
                 raise ops.L.SempyrError("augment: the transform runs inside this package's Discriminator's ingest pass; a caller's own "
                                         "discriminator module cannot be armed")
             self.logger.hyperparameter['augment'] = ",".join([w for w, bit in ops._AUG_WORDS.items() if self._aug_policy & bit]
-                                                              + [w for w, bit in ops._GEOM_WORDS.items() if self._aug_geom & bit])
+                                                              + [w for w, bit in ops._GEOM_WORDS.items() if self._aug_geom & bit]
+                                                              + [w for w, bit in ops._CMAT_WORDS.items() if self._aug_cmat & bit])
         # augment_p: the probability with which an image in front of D is transformed (with augment only).  None: CFG.augment_p
         # (SP_AUGMENT_P); "" = off: every image, nothing below exists.  A number in [0, 1]: fixed.  "adaptive" / "adaptive:<target>" or an
         # ops.AdaptiveAugment: steered on the device.  _ada owns the device state; it is allocated HERE, outside any graph's pool.
@@ -211,6 +216,8 @@ class ModelWrapper(object):
         self._fake_ahead = None
         # the step's (3, B, 8) affine tables of the geometric augmentation where the discriminator phase has decoded them (_d_phase)
         self._aug_tables = None
+        # likewise the step's (3, B, 12) color matrices
+        self._aug_ctables = None
         self._capturing = False
         self._fired = set()
         self.iterations = 0
@@ -327,7 +334,7 @@ class ModelWrapper(object):
                 return None
         if isinstance(spec, bool) or spec is None:
             raise ops.L.SempyrError("augment_p takes a probability in [0, 1], 'adaptive', 'adaptive:<target>' or an ops.AdaptiveAugment (got %r)" % (spec,))
-        if not (self._aug_policy or self._aug_geom):
+        if not (self._aug_policy or self._aug_geom or self._aug_cmat):
             raise ops.L.SempyrError("augment_p=%r, but this ModelWrapper augments nothing (augment / SP_AUGMENT): there is nothing to gate" % (spec,))
         device = next(self.discriminator.parameters()).device
         if isinstance(spec, ops.AdaptiveAugment):
@@ -420,7 +427,7 @@ class ModelWrapper(object):
 
     def _augment_rows(self, images_real, augment_u):
         """The step's (3, B, 8) uniforms (_uniform_rows) - or None with augmentation off.  Drawn FIRST in a step (before the latents)."""
-        return self._uniform_rows(images_real, augment_u, 8, self._aug_policy or self._aug_geom, "augment_u",
+        return self._uniform_rows(images_real, augment_u, 8, self._aug_policy or self._aug_geom or self._aug_cmat, "augment_u",
                                   "augments nothing (augment / SP_AUGMENT)")
 
     def _augment_geom_rows(self, images_real, augment_v):
@@ -428,6 +435,19 @@ class ModelWrapper(object):
         (3, B, 8) draw and in front of the latents."""
         return self._uniform_rows(images_real, augment_v, 4, self._aug_geom, "augment_v",
                                   "has no geometric augmentation (xflip / rot90 / scale / rotate in augment / SP_AUGMENT)")
+
+    def _augment_cmat_rows(self, images_real, augment_z):
+        """The step's (3, B, 8) uniforms of the color-matrix words (_uniform_rows) - or None without them.  Drawn right behind the draw of
+        the geometric words (or the first draw where there are none) and in front of the latents."""
+        return self._uniform_rows(images_real, augment_z, 8, self._aug_cmat, "augment_z",
+                                  "has no color-matrix augmentation (brightness / contrast / lumaflip / hue / saturation in augment / SP_AUGMENT)")
+
+    def _augment_ctables(self, images_real, aug_z, out=None):
+        """The step's (3, B, 12) color matrices: all 3B rows in ONE decode launch (into `out`, the graphs' static buffer, if given) - or
+        None without color-matrix words."""
+        if aug_z is None:
+            return None
+        return ops.augment_cmat_decode(aug_z, self._aug_cmat, out=out).view(3, images_real.shape[0], 12)
 
     def _augment_tables(self, images_real, aug_u, aug_v, out=None):
         """The step's (3, B, 8) affine tables: all 3B rows in ONE decode launch (into `out`, the graphs' static buffer, if given) - or
@@ -437,13 +457,15 @@ class ModelWrapper(object):
         b, _, h, w = images_real.shape
         return ops.augment_geom_decode(aug_u, aug_v, h, w, self._aug_policy, self._aug_geom, out=out).view(3, b, 8)
 
-    def _d_call(self, fn, rows, *args, tables=None):
+    def _d_call(self, fn, rows, *args, tables=None, ctables=None):
         """fn(*args) - the discriminator's forward or forward_pair - armed with these rows of uniforms (and, with geometric words, their
-        affine tables) for that one call (None: as it is)."""
+        affine tables; with color-matrix words, their color matrices) for that one call (None: as it is)."""
         if rows is None:
             return fn(*args)
         D = self.discriminator
-        if tables is not None:
+        if ctables is not None:
+            rows = tuple(zip(rows, tables if tables is not None else (None,) * len(rows), ctables))
+        elif tables is not None:
             rows = tuple(zip(rows, tables))
         D._augment = (self._aug_policy,) + tuple(rows)
         D._augment_p = self._ada.p if self._ada is not None else None
@@ -454,15 +476,17 @@ class ModelWrapper(object):
             D._augment_p = None
 
     def _d_phase(self, images_real, labels, labels_f, masks, noise_d, features_real=None, noise_g=None, aug_u=None, aug_v=None,
-                 aug_t_out=None):
+                 aug_t_out=None, aug_z=None, aug_c_out=None):
         """model_wrapper.py:136-160: forward passes and backward of the discriminator step (everything but Adam).  features_real: the
         pyramid of images_real where an earlier generator step has already computed it (_g_rest, next_images_real).  noise_g: the
         latents of the generator step, for the case that its forward is taken in the same pass as this step's (_g_pair_ok).  aug_u: the
         step's uniforms (_augment_rows) - D sees T(real; aug_u[0]) and T(fake; aug_u[1]); the generator and the VGG-16 see the images.
         aug_v: the uniforms of the geometric words (_augment_geom_rows); their tables are decoded HERE - one launch, inside the first
-        captured graph - into aug_t_out (or a fresh tensor) and left in self._aug_tables for the generator step."""
+        captured graph - into aug_t_out (or a fresh tensor) and left in self._aug_tables for the generator step.  aug_z: the uniforms of the
+        color-matrix words (_augment_cmat_rows), decoded likewise into aug_c_out and left in self._aug_ctables."""
         G, D, V = self.generator, self.discriminator, self.vgg16
         aug_t = self._aug_tables = self._augment_tables(images_real, aug_u, aug_v, aug_t_out)
+        aug_c = self._aug_ctables = self._augment_ctables(images_real, aug_z, aug_c_out)
         G.zero_grad()
         D.zero_grad()
         self._fake_ahead = None
@@ -484,12 +508,13 @@ class ModelWrapper(object):
         if CFG.d_pair and hasattr(D, "forward_pair") and D.training and images_fake.shape == images_real.shape:
             rows = None if aug_u is None else (aug_u[0], aug_u[1])
             prediction_real, prediction_fake = self._d_call(D.forward_pair, rows, images_real, images_fake, labels,
-                                                            tables=None if aug_t is None else (aug_t[0], aug_t[1]))     # one trunk pass over 2B images
+                                                            tables=None if aug_t is None else (aug_t[0], aug_t[1]),
+                                                            ctables=None if aug_c is None else (aug_c[0], aug_c[1]))     # one trunk pass over 2B images
         else:
             prediction_real = self._d_call(D, None if aug_u is None else (aug_u[0],), images_real, labels,
-                                           tables=None if aug_t is None else (aug_t[0],))
+                                           tables=None if aug_t is None else (aug_t[0],), ctables=None if aug_c is None else (aug_c[0],))
             prediction_fake = self._d_call(D, None if aug_u is None else (aug_u[1],), images_fake, labels,
-                                           tables=None if aug_t is None else (aug_t[1],))
+                                           tables=None if aug_t is None else (aug_t[1],), ctables=None if aug_c is None else (aug_c[1],))
         if self._adaptive():
             # the overfitting signal's counts (sp_ada_observe): one launch on D's fp32 predictions, inside the first captured graph; p
             # itself moves only behind Adam(G) (train_step), so every gate of this step reads the same value
@@ -556,7 +581,7 @@ class ModelWrapper(object):
         return loss_div, features_fake, features_next
 
     def _g_rest(self, images_fake, noise_g, labels, masks, features_real, w_rec, w_div, next_images_real=None, features_next_out=None,
-                ahead=None, aug_u=None, aug_t=None):
+                ahead=None, aug_u=None, aug_t=None, aug_c=None):
         """model_wrapper.py:174-188: D(fake), the generator and reconstruction losses, backward (everything but Adam).  aug_u: the step's
         uniforms - D sees T(fake; aug_u[2]), whose backward carries D's image gradient through T; every other loss sees the images.  ahead: what
         _g_features has already computed for these fake images (train_step: in front of the discriminator's optimizer step); without
@@ -571,7 +596,7 @@ class ModelWrapper(object):
             p.requires_grad_(False)
         try:
             prediction_fake = self._d_call(D, None if aug_u is None else (aug_u[2],), images_fake, labels,
-                                           tables=None if aug_t is None else (aug_t[2],))
+                                           tables=None if aug_t is None else (aug_t[2],), ctables=None if aug_c is None else (aug_c[2],))
             loss_g = self.generator_loss(prediction_fake)
             if isinstance(self.semantic_reconstruction_loss, SemanticReconstructionLoss):
                 loss_rec = self.semantic_reconstruction_loss(features_real, features_fake, masks, weight=w_rec)
@@ -609,11 +634,11 @@ class ModelWrapper(object):
     def train_step(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1,
                    noise_d: Optional[torch.Tensor] = None, noise_g: Optional[torch.Tensor] = None,
                    next_images_real: Optional[torch.Tensor] = None, augment_u: Optional[torch.Tensor] = None,
-                   augment_v: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   augment_v: Optional[torch.Tensor] = None, augment_z: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """One iteration of model_wrapper.py:131-190 on tensors already on the device.  ``noise_d`` / ``noise_g``
         replace the two ``torch.randn`` draws (model_wrapper.py:147,168) for parity runs, ``augment_u`` ((3, B, 8), with augmentation
         on only) the ``torch.rand`` draw in front of them, ``augment_v`` ((3, B, 4), with geometric words only) the one right behind
-        it.  Returns the loss scalars as device tensors (no host sync).
+        it, ``augment_z`` ((3, B, 8), with color-matrix words only) the one behind that.  Returns the loss scalars as device tensors (no host sync).
 
         ``next_images_real`` (optional): the real images of the NEXT call (the same tensor object must then be passed as its
         ``images_real``).  The frozen VGG-16 sees them in the pass it makes over this iteration's fake images - one pass over 2B
@@ -632,9 +657,10 @@ class ModelWrapper(object):
         labels_f = idx if isinstance(self.generator, Generator) else raw_labels
         aug_u = self._augment_rows(images_real, augment_u)
         aug_v = self._augment_geom_rows(images_real, augment_v)
+        aug_z = self._augment_cmat_rows(images_real, augment_z)
         with profiling.range("D phase"):
             features_real, loss_d_real, loss_d_fake = self._d_phase(images_real, labels, labels_f, masks, noise_d,
-                                                                      self._features_ahead(images_real), noise_g, aug_u, aug_v)
+                                                                      self._features_ahead(images_real), noise_g, aug_u, aug_v, aug_z=aug_z)
             self._start_reduce("d", self._d_params, eager=True)
         with profiling.range("G forward"):
             images_fake, noise_g = self._g_forward(images_real, labels_f, masks, features_real, noise_g)
@@ -644,7 +670,7 @@ class ModelWrapper(object):
             self._optimizer_step("d", self.discriminator_optimizer)
         with profiling.range("G rest"):
             loss_g, loss_rec, loss_div = self._g_rest(images_fake, noise_g, labels, masks, features_real, w_rec, w_div, next_images_real,
-                                                      ahead=ahead, aug_u=aug_u, aug_t=self._aug_tables)
+                                                      ahead=ahead, aug_u=aug_u, aug_t=self._aug_tables, aug_c=self._aug_ctables)
             self._start_reduce("g", self._g_params, eager=True)
         with profiling.range("Adam(G)"):
             self._join_reduce("g")
@@ -686,10 +712,13 @@ class ModelWrapper(object):
         # the step's uniforms of the augmentation: a static buffer the transform launches INSIDE the graphs decode on the device;
         # train_step_graphed refills it in front of every replay (None with augmentation off: no buffer, no draw)
         st["augment_u"] = (torch.zeros((3, zdim[0], 8), dtype=torch.float32, device=images_real.device)
-                           if self._aug_policy or self._aug_geom else None)
+                           if self._aug_policy or self._aug_geom or self._aug_cmat else None)
         # likewise the uniforms of the geometric words and the tables the first graph's decode launch writes and all three transforms read
         st["augment_v"] = torch.zeros((3, zdim[0], 4), dtype=torch.float32, device=images_real.device) if self._aug_geom else None
         st["augment_t"] = torch.zeros((3 * zdim[0], 8), dtype=torch.float32, device=images_real.device) if self._aug_geom else None
+        # and the uniforms of the color-matrix words with the matrices the first graph's second decode launch writes
+        st["augment_z"] = torch.zeros((3, zdim[0], 8), dtype=torch.float32, device=images_real.device) if self._aug_cmat else None
+        st["augment_c"] = torch.zeros((3 * zdim[0], 12), dtype=torch.float32, device=images_real.device) if self._aug_cmat else None
         # The pyramid of the real images is computed AHEAD (config.CFG.vgg_pair): the generator-step graph takes the next batch's real
         # images (st["images_next"]) through the VGG pass it makes over the fake images and leaves their features in st["feats_real"],
         # which the discriminator-step graph of the next replay reads.  Eager once here, so that the first replay finds them.
@@ -718,7 +747,7 @@ class ModelWrapper(object):
                 lab_d = cls if isinstance(self.discriminator, Discriminator) else st["labels"]      # (a caller's own module gets what it was written for)
                 lab_g = cls if isinstance(self.generator, Generator) else st["labels"]
                 feats, l_real, l_fake = self._d_phase(st["images"], lab_d, lab_g, st["masks"], st["noise_d"], st["feats_real"], st["noise_g"],
-                                                      st["augment_u"], st["augment_v"], st["augment_t"])
+                                                      st["augment_u"], st["augment_v"], st["augment_t"], st["augment_z"], st["augment_c"])
             st["lecam_reg"] = self._lecam_reg                      # (None with LeCam off) the first graph's static output
             st["d_grads"] = [p.grad for p in self._d_params]
             # second graph: what the generator step can do in front of the discriminator's optimizer step - its forward, unless that rode
@@ -731,7 +760,8 @@ class ModelWrapper(object):
             gg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gg, pool=gd.pool()):
                 l_g, l_rec, l_div = self._g_rest(fake, st["noise_g"], lab_d, st["masks"], feats, w_rec, w_div, st.get("images_next"),
-                                                 st["feats_real"], ahead=ahead, aug_u=st["augment_u"], aug_t=self._aug_tables)
+                                                 st["feats_real"], ahead=ahead, aug_u=st["augment_u"], aug_t=self._aug_tables,
+                                                 aug_c=self._aug_ctables)
             st["g_grads"] = [p.grad for p in self._g_params]
         except BaseException:
             ops.drop_wgrad_reduce()            # queued slab reductions of the abandoned capture point into its (released) pool
@@ -764,7 +794,7 @@ class ModelWrapper(object):
     def train_step_graphed(self, images_real: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, masks=None,
                            noise_d: Optional[torch.Tensor] = None, noise_g: Optional[torch.Tensor] = None,
                            next_images_real: Optional[torch.Tensor] = None, augment_u: Optional[torch.Tensor] = None,
-                           augment_v: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                           augment_v: Optional[torch.Tensor] = None, augment_z: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """train_step() through the captured graphs (capture_graphs() first).  images / labels / masks: new batch to copy into
         the graphs' static inputs, or None to reuse the resident one.  next_images_real: as in train_step() - the next call's real
         images, whose VGG pyramid this call computes ahead; without it (and outside the resident mode) the next call computes its
@@ -787,6 +817,12 @@ class ModelWrapper(object):
             st["augment_v"].uniform_()                          # right behind the first draw, as train_step() draws
         else:
             st["augment_v"].copy_(self._augment_geom_rows(st["images"], augment_v))
+        if st.get("augment_z") is None:
+            self._augment_cmat_rows(st["images"], augment_z)    # (no color-matrix words: raises if the caller brings uniforms)
+        elif augment_z is None:
+            st["augment_z"].uniform_()                          # behind the draws above and in front of the latents, as train_step() draws
+        else:
+            st["augment_z"].copy_(self._augment_cmat_rows(st["images"], augment_z))
         if noise_d is None:
             st["noise_d"].normal_()
         else:

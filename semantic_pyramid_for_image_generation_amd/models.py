@@ -727,8 +727,11 @@ class Generator(nn.Module):
 # discriminator
 # --------------------------------------------------------------------------------------------------
 def _aug_row(row):
-    """One armed row of Discriminator._augment: u alone, or (u, table) with geometric words -> (u, table or None)."""
-    return row if isinstance(row, tuple) else (row, None)
+    """One armed row of Discriminator._augment: u alone, (u, table) with geometric words, or (u, table or None, ctable) with
+    color-matrix words -> (u, table or None, ctable or None)."""
+    if not isinstance(row, tuple):
+        return row, None, None
+    return row if len(row) == 3 else (row[0], row[1], None)
 
 
 class Discriminator(nn.Module):
@@ -760,6 +763,7 @@ class Discriminator(nn.Module):
         # (policy mask, u) for forward or (policy mask, u_a, u_b) for forward_pair and clears it behind the call.  None: the plain ingest.
         # _augment_p rides with it: None, or the gate's probability (a 1-element fp32 device tensor, ops.AdaptiveAugment.p) of that call.
         # With geometric words each row is a pair (u, table): the batch's affine table of ops.augment_geom_decode.
+        # With color-matrix words, and only then, a triple (u, table or None, ctable): ops.augment_cmat_decode's rows.
         self._augment = None
         self._augment_p = None
 
@@ -769,8 +773,10 @@ class Discriminator(nn.Module):
             return ops.ingest_image(input, dt)
         if len(aug) != 2:
             raise ops.L.SempyrError("Discriminator.forward: armed for forward_pair (two rows of uniforms)")
-        u, table = _aug_row(aug[1])
-        return ops.augment_ingest_image(input, dt, u, aug[0], p=getattr(self, "_augment_p", None), table=table)
+        u, table, ctable = _aug_row(aug[1])
+        if ctable is None:
+            return ops.augment_ingest_image(input, dt, u, aug[0], p=getattr(self, "_augment_p", None), table=table)
+        return ops.augment_ingest_image(input, dt, u, aug[0], p=getattr(self, "_augment_p", None), table=table, ctable=ctable)
 
     def forward(self, input: torch.Tensor, class_id: torch.Tensor) -> torch.Tensor:
         dt = ops.compute_dtype()
@@ -834,9 +840,9 @@ class Discriminator(nn.Module):
             if aug is None:
                 x = ops.ingest_image_pair(input_a, input_b, dt)
             else:
-                (u_a, t_a), (u_b, t_b) = _aug_row(aug[1]), _aug_row(aug[2])
+                (u_a, t_a, c_a), (u_b, t_b, c_b) = _aug_row(aug[1]), _aug_row(aug[2])
                 x = ops.augment_ingest_image_pair(input_a, input_b, dt, u_a, u_b, aug[0], p=getattr(self, "_augment_p", None),
-                                                  table_a=t_a, table_b=t_b)
+                                                  table_a=t_a, table_b=t_b, **({} if c_a is None else {"ctable": (c_a, c_b)}))
             x = L[0](x)
             x = L[3](L[2](L[1](x)))
             x = L[7](L[6](L[5](L[4](x))))

@@ -1883,6 +1883,95 @@ def augment_geom_decode(u: torch.Tensor, v: torch.Tensor, h: int, w: int, policy
     return out
 
 
+# ADA's color group (csrc/augment.hip: THE COLOR MATRIX): a third mask, so that augment_policy and augment_geom keep refusing
+# what they refused
+CMAT_BRIGHTNESS, CMAT_CONTRAST, CMAT_LUMAFLIP, CMAT_HUE, CMAT_SATURATION = 1, 2, 4, 8, 16
+_CMAT_WORDS = {"brightness": CMAT_BRIGHTNESS, "contrast": CMAT_CONTRAST, "lumaflip": CMAT_LUMAFLIP, "hue": CMAT_HUE,
+               "saturation": CMAT_SATURATION}
+
+
+def augment_cmat(words) -> int:
+    """"brightness,contrast,lumaflip,hue,saturation" (any subset, any order; "" / None = none) or the bit mask itself -> the bit mask of
+    include/sempyr.h's SP_CMAT_*.  An unknown word raises (the words of the other two families included: augment_split3 takes all)."""
+    return _word_mask(words, _CMAT_WORDS, "color-matrix augmentation")
+
+
+def augment_split3(policy):
+    """One comma-separated string holding words of all three families (or None, or augment_policy's bit mask) -> (policy bits, geom
+    bits, cmat bits).  Without color-matrix words: augment_split(policy) + (0,), raising where augment_split raises."""
+    if not isinstance(policy, str):
+        return augment_split(policy) + (0,)
+    words = [w.strip() for w in policy.split(",")]
+    cmat = augment_cmat(",".join(w for w in words if w in _CMAT_WORDS))
+    return augment_split(",".join(w for w in words if w not in _CMAT_WORDS)) + (cmat,)
+
+
+def augment_cmat_table(z: torch.Tensor, cmat, dtype=torch.float32) -> torch.Tensor:
+    """The decode launch's ctable ((n, 12): L00 L01 L02 t L10 L11 L12 t L20 L21 L22 t) restated on the host from z (n, 8), operation by
+    operation in `dtype`: fp32 gives the kernel's bits for rows without brightness, contrast, hue and saturation and the kernel's
+    expressions around the host's log / sqrt / cos / sin / exp2 otherwise; float64 is the reference.  A part left out is not
+    computed: its factor is the constant (no libm call)."""
+    cmat = augment_cmat(cmat)
+    z = z.detach().to("cpu", torch.float32)
+    if z.dim() != 2 or z.shape[1] != 8:
+        raise L.SempyrError("augment_cmat_table: z must be (n, 8), got %s" % (tuple(z.shape),))
+    n = z.shape[0]
+    const = lambda x: torch.tensor(x, dtype=torch.float32).to(dtype)      # noqa: E731  (the kernel's fp32 constants)
+    zz = z.to(dtype)
+    one, zero = torch.ones(n, dtype=dtype), torch.zeros(n, dtype=dtype)
+
+    def nrm(a, b):          # Box-Muller: sqrtf(-2 * logf(1 - a)) * cosf(float(2 pi) * b)
+        return torch.sqrt(-2.0 * torch.log(1.0 - zz[:, a])) * torch.cos(const(2.0 * math.pi) * zz[:, b])
+    bb, c, s, cs, sn, f = zero, one, one, one, zero, one
+    if cmat & CMAT_BRIGHTNESS:
+        bb = const(0.2) * nrm(0, 1)
+    if cmat & CMAT_CONTRAST:
+        c = torch.exp2(0.5 * nrm(2, 3))
+    if cmat & CMAT_SATURATION:
+        s = torch.exp2(nrm(4, 5))
+    if cmat & CMAT_HUE:
+        theta = (2.0 * zz[:, 6] - 1.0) * const(math.pi)
+        cs, sn = torch.cos(theta), torch.sin(theta)
+    if cmat & CMAT_LUMAFLIP:
+        f = torch.where(z[:, 7] < 0.5, -one, one)
+    p, cs_ = c * f, c * s
+    # 1 / sqrt 3 belongs to the closed form (K is a cross-product matrix only with it), not to the draw: rounded to `dtype`, not to fp32
+    beta, gamma = cs_ * cs, (cs_ * sn) * torch.tensor(1.0 / math.sqrt(3.0), dtype=dtype)
+    d = (p - beta) / 3.0
+    di, lo, hi, t = beta + d, d - gamma, d + gamma, p * bb
+    return torch.stack([di, lo, hi, t, hi, di, lo, t, lo, hi, di, t], dim=1)
+
+
+def augment_cmat_decode(z: torch.Tensor, cmat, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ONE launch (include/sempyr.h: sp_augment_cmat_decode): the color matrices of all rows of z (..., 8), contiguous fp32 on the GPU
+    -> (rows, 12) fp32 (into `out` if given).  augment_cmat_table restates it on the host."""
+    cmat = augment_cmat(cmat)
+    require_gpu(z)
+    ok = lambda t, k: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() >= 2 and t.shape[-1] == k      # noqa: E731
+    if not (ok(z, 8) and z.numel() > 0):
+        raise L.SempyrError("augment_cmat_decode: z (..., 8) must be a contiguous fp32 tensor on the GPU (got %s %s)" % (tuple(z.shape), z.dtype))
+    n = z.numel() // 8
+    if out is None:
+        out = torch.empty((n, 12), dtype=torch.float32, device=z.device)
+    elif not (ok(out, 12) and out.numel() == n * 12 and out.device == z.device):
+        raise L.SempyrError("augment_cmat_decode: out must be a contiguous fp32 tensor of %d x 12 on z's GPU" % n)
+    L.call("sp_augment_cmat_decode", ptr(z), n, cmat, ptr(out), stream())
+    return out
+
+
+def _augment_ctable(ctable, n, device):
+    """The color matrices of the sp_augment_cmat_* entries: contiguous fp32 (n, 12) on the images' GPU, 16-byte aligned.  None: the
+    entries without one."""
+    if ctable is None:
+        return None
+    if not (isinstance(ctable, torch.Tensor) and ctable.is_cuda and ctable.device == device and ctable.dtype == torch.float32
+            and tuple(ctable.shape) == (n, 12) and ctable.is_contiguous() and ctable.data_ptr() % 16 == 0):
+        raise L.SempyrError("the color-matrix augmenting ingest takes ctable as a contiguous, 16-byte aligned fp32 (n, 12) tensor on the "
+                            "images' GPU, one row per image (got %r for %d images)"
+                            % (((tuple(ctable.shape), ctable.dtype, str(ctable.device)) if isinstance(ctable, torch.Tensor) else ctable), n))
+    return ctable
+
+
 def _augment_table(table, n, device):
     """The affine table of the geometric entries: contiguous fp32 (n, 8) on the images' GPU.  None: the existing entries."""
     if table is None:
@@ -1939,10 +2028,13 @@ def _augment_gate(p, device):
     return p
 
 
-def _augment_entry(backward, p, table, part):
-    """(name, arguments between `policy` and `dtype`) of the entry for this call - include/sempyr.h: the geometric entries with a table
-    (p may be NULL there), the gated ones with p alone, else the plain ones."""
+def _augment_entry(backward, p, table, part, ctable=None):
+    """(name, arguments between `policy` and `dtype`) of the entry for this call - include/sempyr.h: the color-matrix entries with a
+    ctable (table and p may be NULL there), the geometric entries with a table (p may be NULL there), the gated ones with p alone,
+    else the plain ones."""
     bwd = "_bwd" if backward else ""
+    if ctable is not None:
+        return "sp_augment_cmat_ingest" + bwd, (ptr(table), ptr(ctable), ptr(part), ptr(p))
     if table is not None:
         return "sp_augment_geom_ingest" + bwd, (ptr(table), ptr(part), ptr(p))
     if p is not None:
@@ -1950,11 +2042,11 @@ def _augment_entry(backward, p, table, part):
     return "sp_augment_ingest" + bwd, (ptr(part),)
 
 
-def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None, table=None):
+def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None, table=None, ctable=None):
     n, _, h, w = img.shape
     sn, scs, sh, sw = img.stride()
     part = _augment_partials(n, h, w, policy, False, img.device, table is not None)
-    name, extra = _augment_entry(False, p, table, part)
+    name, extra = _augment_entry(False, p, table, part, ctable)
     L.call(name, ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, *extra, sp_dtype(dtype), stream())
 
 
@@ -1962,11 +2054,12 @@ class _AugmentIngestFn(torch.autograd.Function):
     """_IngestFn with the augmentation applied in the same pass: T(img; u) -> NHWC with zero-padded channels; gradients flow through T."""
 
     @staticmethod
-    def forward(ctx, img, dtype, u, policy, p=None, table=None):
+    def forward(ctx, img, dtype, u, policy, p=None, table=None, ctable=None):
         n, c, h, w = img.shape
         cp = pad_channels(c, dtype)
         y = nhwc_empty(n, cp, h, w, dtype, img.device)
-        _augment_fwd(img, ptr(y), dtype, cp, u, policy, p, table)
+        _augment_fwd(img, ptr(y), dtype, cp, u, policy, p, table, ctable)
+        ctx.ctable = ctable                # None: the entries without one; else the backward applies the transposed matrices of the same rows
         ctx.cfg = (n, h, w, cp, policy, img.dtype)
         ctx.u = u
         ctx.table = table                  # None: the existing entries; else the geometric ones, whose backward gathers through the same table
@@ -1979,31 +2072,35 @@ class _AugmentIngestFn(torch.autograd.Function):
         dy = as_nhwc(dy)
         dsrc = nhwc_empty(n, 3, h, w, dy.dtype, dy.device)
         part = _augment_partials(n, h, w, policy, True, dy.device, ctx.table is not None)
-        name, extra = _augment_entry(True, ctx.p, ctx.table, part)
+        name, extra = _augment_entry(True, ctx.p, ctx.table, part, ctx.ctable)
         L.call(name, ptr(dy), cp, ptr(dsrc), n, h, w, ptr(ctx.u), policy, *extra, sp_dtype(dy.dtype), stream())
         if dsrc.dtype != src_dtype:
             dsrc = dsrc.to(src_dtype)
-        return dsrc, None, None, None, None, None
+        return dsrc, None, None, None, None, None, None
 
 
 def augment_ingest_image(img: torch.Tensor, dtype, u: torch.Tensor, policy, p: Optional[torch.Tensor] = None,
-                         table: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         table: Optional[torch.Tensor] = None, ctable: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ingest_image(T(img; u), dtype) in the ingest's own pass (csrc/augment.hip): u = (n, 8) fp32 uniforms on the device, one row per
     image, decoded in the kernel (augment_decode restates it); policy = "color,translation,cutout", a subset, or the bit mask.
     p: None, or the gate - a 1-element fp32 device tensor read when the kernels run: image i is transformed iff u[i, 7] < p, else it
     is ingested as ingest_image does it, bit for bit, forward and backward (AdaptiveAugment.p is such a tensor).
     table: None, or the (n, 8) affine table of augment_geom_decode: the geometric entries then resample the image through it (bilinear,
-    zero padding; the backward is the adjoint by gather) and take the policy's color and cutout bits only - the translation is in the table."""
+    zero padding; the backward is the adjoint by gather) and take the policy's color and cutout bits only - the translation is in the table.
+    ctable: None, or the (n, 12) color matrices of augment_cmat_decode (any 3 x 4 matrices): the color-matrix entries then apply row i to
+    every source pixel of image i as the last step of its color stage, in either family; the backward applies the transposed matrix."""
     policy = _augment_args(img, u, policy)
-    return _AugmentIngestFn.apply(img, dtype, u, policy, _augment_gate(p, img.device), _augment_table(table, img.shape[0], img.device))
+    return _AugmentIngestFn.apply(img, dtype, u, policy, _augment_gate(p, img.device), _augment_table(table, img.shape[0], img.device),
+                                  _augment_ctable(ctable, img.shape[0], img.device))
 
 
 def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u_a: torch.Tensor, u_b: torch.Tensor, policy,
                               p: Optional[torch.Tensor] = None, table_a: Optional[torch.Tensor] = None,
-                              table_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+                              table_b: Optional[torch.Tensor] = None, ctable=None) -> torch.Tensor:
     """ingest_image_pair with each batch under its own transform: ONE padded NHWC batch [T(a; u_a) | T(b; u_b)], no autograd of
     its own (the discriminator step needs no image gradient).  p: the gate of augment_ingest_image, for both batches.  table_a /
-    table_b: both None, or each batch's affine table (augment_ingest_image's table)."""
+    table_b: both None, or each batch's affine table (augment_ingest_image's table).  ctable: None, or the pair (ctable_a, ctable_b) of
+    the batches' color matrices (augment_ingest_image's ctable)."""
     with torch.no_grad():
         img_a, img_b = img_a.detach(), img_b.detach()
         policy = _augment_args(img_a, u_a, policy)
@@ -2018,8 +2115,13 @@ def augment_ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, u
         if (table_a is None) != (table_b is None):
             raise L.SempyrError("augment_ingest_image_pair: give both tables or none")
         table_a, table_b = _augment_table(table_a, na, img_a.device), _augment_table(table_b, img_b.shape[0], img_a.device)
-        for img, u, t, off in ((img_a, u_a, table_a, 0), (img_b, u_b, table_b, na)):
-            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy, p, t)
+        if ctable is None:
+            ctable = (None, None)
+        elif not (isinstance(ctable, (tuple, list)) and len(ctable) == 2 and ctable[0] is not None and ctable[1] is not None):
+            raise L.SempyrError("augment_ingest_image_pair: ctable is None or the pair (ctable_a, ctable_b)")
+        ct_a, ct_b = _augment_ctable(ctable[0], na, img_a.device), _augment_ctable(ctable[1], img_b.shape[0], img_a.device)
+        for img, u, t, ct, off in ((img_a, u_a, table_a, ct_a, 0), (img_b, u_b, table_b, ct_b, na)):
+            _augment_fwd(img, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz), dtype, cp, u, policy, p, t, ct)
     return y
 
 
