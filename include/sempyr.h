@@ -474,6 +474,13 @@ int sp_attention_route(int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dty
  * models.py:195-197; scale3/shift3 are HOST pointers to 3 floats), mask application (models.py:78,80,94),
  * activations, attention residual (models.py:274), NCHW-flatten <-> NHWC permutation (models.py:83,208),
  * per-channel sums (bias gradients).
+ * Every entry of this group refuses, before any launch, a `dtype` other than SP_F32 / SP_BF16 / SP_F16 with SP_ERR_UNSUPPORTED
+ * (SP_F8 and SP_F8_F16 included: these kernels have no fp8 form); sp_act_fwd / sp_act_bwd refuse an `act` outside sp_act likewise.
+ * src_dtype is SP_F32 or the storage type itself.  The two 16-bit types never mix, in sp_ingest_image and in every sp_augment_*_ingest
+ * entry with a src_dtype: an SP_BF16 source under SP_F16 storage, and an SP_F16 source under SP_BF16 or SP_F32 storage, are
+ * SP_ERR_UNSUPPORTED and nothing is launched (each compilation of the kernels decodes a 16-bit source as ITS 16-bit type).
+ * sp_act_fwd: NONE copies, LeakyReLU is max(v, fl32(0.2f v)), ReLU(NaN) = 0 (fmaxf, as the convolution epilogues' v > 0 ? v : 0), NaN
+ * passes through the other three.  DESIGN.md section 21.
  * ---------------------------------------------------------------------------------------------- */
 int sp_ingest_image(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* dst,
                     int32_t n, int32_t c, int32_t h, int32_t w_, int32_t cp, const float* scale3,

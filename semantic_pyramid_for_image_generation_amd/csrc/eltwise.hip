@@ -12,6 +12,15 @@ inline int grid_for(long work_items) {
     return (int)b;
 }
 
+// The value as an fp32 register.  Every result of this file is formed in fp32 and THEN rounded once into the storage type, which is
+// what the packed conversions of st4 do.  In front of a single-element store the fp16 compilation otherwise folds the last multiply(-add)
+// and the conversion into v_fma_mixlo_f16, which rounds the exact product once into fp16: another value at the ties of the double
+// rounding (2 of 1536 elements of an ingest gradient), so the scalar and the vector kernel of one entry would disagree.
+__device__ __forceinline__ float fl32(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 // ---- image ingest: strided 3-channel source -> NHWC with zero-padded channels, optional affine ------
 template <typename TS, typename TD>
 __global__ void ingest_kernel(const TS* __restrict__ src, long sn, long sc, long sh, long sw, TD* __restrict__ dst,
@@ -27,7 +36,7 @@ __global__ void ingest_kernel(const TS* __restrict__ src, long sn, long sc, long
         for (int c = 0; c < CP; ++c) {
             float v = 0.f;
             if (c < C) v = Elem<TS>::ld(s + c * sc) * sc3[c % 3] + sf3[c % 3];
-            Elem<TD>::st(dst + p * CP + c, v);
+            Elem<TD>::st(dst + p * CP + c, fl32(v));
         }
     }
 }
@@ -37,7 +46,7 @@ template <typename T>
 __global__ void ingest_bwd_kernel(const T* __restrict__ dy, int CP, T* __restrict__ dsrc, int C, long pixels, float3 scale) {
     const float sc3[3] = {scale.x, scale.y, scale.z};
     for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long)gridDim.x * 256)
-        for (int c = 0; c < C; ++c) Elem<T>::st(dsrc + p * C + c, Elem<T>::ld(dy + p * CP + c) * sc3[c % 3]);
+        for (int c = 0; c < C; ++c) Elem<T>::st(dsrc + p * C + c, fl32(Elem<T>::ld(dy + p * CP + c) * sc3[c % 3]));
 }
 
 // ---- feature * mask, concatenated with the mask channel (models.py:94), padded to CP channels ------
@@ -75,7 +84,7 @@ __global__ void mask_mul_2d_kernel(const T* __restrict__ feat, int ldf, const fl
         const int b = (int)(i / ldo), k = (int)(i % ldo);
         float v = 0.f;
         if (k < K) v = Elem<T>::ld(feat + (long)b * ldf + k) * mask[(long)b * K + k];
-        Elem<T>::st(out + i, v);
+        Elem<T>::st(out + i, fl32(v));
     }
 }
 
@@ -119,7 +128,7 @@ __global__ void act_bwd_pad_kernel(const T* __restrict__ dy, const T* __restrict
         const int c = (int)(i - p * CP);
         float v = 0.f;
         if (c < C) v = act_grad(Elem<T>::ld(dy + p * C + c), Elem<T>::ld(y + p * C + c), act);
-        Elem<T>::st(dz + i, v);
+        Elem<T>::st(dz + i, fl32(v));
     }
 }
 
@@ -164,7 +173,7 @@ __global__ void rescale_bias_scalar_kernel(const T* __restrict__ x, T* __restric
         const long row = i / c;
         const int col = (int)(i - row * c);
         const float bv = bias != nullptr ? bias[col] : 0.f;
-        Elem<T>::st(y + row * ldy + col, (Elem<T>::ld(x + row * ldx + col) - bv) * r + bv);
+        Elem<T>::st(y + row * ldy + col, fl32((Elem<T>::ld(x + row * ldx + col) - bv) * r + bv));
     }
 }
 
@@ -254,13 +263,20 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ 
 
 }  // namespace
 
+// storage types of this file (SP_F16 arrives here as SP_BF16 of the fp16 compilation); checked by every entry before SP_DT_SWITCH,
+// whose second branch is the 16-bit kernel
+#define SP_CHECK_DTYPE(dtype, name) do { if ((dtype) != SP_F32 && (dtype) != SP_BF16) { \
+    sp_set_error("%s: dtype %d not supported (SP_F32 / SP_BF16 / SP_F16)", name, (int)(dtype)); return SP_ERR_UNSUPPORTED; } } while (0)
+#define SP_CHECK_ACT(act, name) do { if ((act) < SP_ACT_NONE || (act) > SP_ACT_TANH) { \
+    sp_set_error("%s: act %d not supported (SP_ACT_NONE / LRELU / RELU / TANH)", name, (int)(act)); return SP_ERR_UNSUPPORTED; } } while (0)
 #define SP_DT_SWITCH(dtype, CALL_F32, CALL_BF16) do { if ((dtype) == SP_F32) { CALL_F32; } else { CALL_BF16; } } while (0)
 
 extern "C" int sp_ingest_image(const void* src, int32_t src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw,
                                void* dst, int32_t n, int32_t c, int32_t h, int32_t w_, int32_t cp, const float* scale3,
                                const float* shift3, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(src && dst && c <= 3 && cp >= c, "sp_ingest_image: bad args");
-    SP_CHECK_ARG((src_dtype == SP_F32 || src_dtype == SP_BF16) && (dtype == SP_F32 || dtype == SP_BF16), "sp_ingest_image: bad dtype");
+    SP_CHECK_ARG(src_dtype == SP_F32 || src_dtype == SP_BF16, "sp_ingest_image: bad src_dtype %d", (int)src_dtype);
+    SP_CHECK_DTYPE(dtype, "sp_ingest_image");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float3 sc3 = make_float3(1.f, 1.f, 1.f), sf3 = make_float3(0.f, 0.f, 0.f);
     if (scale3) sc3 = make_float3(scale3[0], scale3[1], scale3[2]);     // host pointers (3 floats)
@@ -281,6 +297,7 @@ extern "C" int sp_ingest_image(const void* src, int32_t src_dtype, int64_t sn, i
 extern "C" int sp_ingest_image_bwd(const void* dy, int32_t cp, void* dsrc, int32_t c, int64_t pixels, const float* scale3,
                                    int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(dy && dsrc && c <= 3 && cp >= c, "sp_ingest_image_bwd: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_ingest_image_bwd");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float3 sc3 = make_float3(1.f, 1.f, 1.f);
     if (scale3) sc3 = make_float3(scale3[0], scale3[1], scale3[2]);
@@ -295,6 +312,7 @@ extern "C" int sp_ingest_image_bwd(const void* dy, int32_t cp, void* dsrc, int32
 extern "C" int sp_mask_concat(const void* feat, const float* mask, void* out, int64_t pixels, int32_t c, int32_t cp,
                               int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(feat && mask && out && cp > c && cp % 4 == 0 && c % 4 == 0, "sp_mask_concat: bad args (c=%d cp=%d)", c, cp);
+    SP_CHECK_DTYPE(dtype, "sp_mask_concat");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int g = grid_for(pixels * (cp / 4));
     SP_DT_SWITCH(dtype,
@@ -307,6 +325,7 @@ extern "C" int sp_mask_concat(const void* feat, const float* mask, void* out, in
 extern "C" int sp_mask_mul_2d(const void* feat, int32_t ldf, const float* mask, void* out, int32_t ldo, int32_t batch,
                               int32_t k, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(feat && mask && out && ldf >= k && ldo >= k, "sp_mask_mul_2d: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_mask_mul_2d");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int g = grid_for((long)batch * ldo);
     SP_DT_SWITCH(dtype,
@@ -318,6 +337,8 @@ extern "C" int sp_mask_mul_2d(const void* feat, int32_t ldf, const float* mask, 
 
 extern "C" int sp_act_fwd(const void* x, void* y, int64_t numel, int32_t act, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(x && y && numel % 4 == 0, "sp_act_fwd: numel must be a multiple of 4");
+    SP_CHECK_DTYPE(dtype, "sp_act_fwd");
+    SP_CHECK_ACT(act, "sp_act_fwd");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int g = grid_for(numel / 4);
     SP_DT_SWITCH(dtype,
@@ -330,6 +351,8 @@ extern "C" int sp_act_fwd(const void* x, void* y, int64_t numel, int32_t act, in
 extern "C" int sp_act_bwd(const void* dy, const void* y, void* dz, int64_t pixels, int32_t c, int32_t cp, int32_t act,
                           int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(dy && y && dz && cp >= c, "sp_act_bwd: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_act_bwd");
+    SP_CHECK_ACT(act, "sp_act_bwd");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (c == cp && (pixels * c) % 4 == 0) {
         const long n4 = pixels * c / 4;
@@ -350,6 +373,7 @@ extern "C" int sp_act_bwd(const void* dy, const void* y, void* dz, int64_t pixel
 extern "C" int sp_scale_add(const void* a, const void* b, const float* g, void* y, int64_t numel, int32_t dtype,
                             sp_stream_t stream) {
     SP_CHECK_ARG(a && b && g && y && numel % 4 == 0, "sp_scale_add: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_scale_add");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int gr = grid_for(numel / 4);
     SP_DT_SWITCH(dtype,
@@ -362,6 +386,7 @@ extern "C" int sp_scale_add(const void* a, const void* b, const float* g, void* 
 extern "C" int sp_rescale_bias(const void* x, void* y, int64_t rows, int32_t c, int32_t ldx, int32_t ldy, const float* bias,
                                const float* sig_a, const float* sig_b, int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(x && y && sig_a && sig_b && rows > 0 && c > 0 && ldx >= c && ldy >= c, "sp_rescale_bias: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_rescale_bias");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if ((c & 3) || (ldx & 3) || (ldy & 3)) {                 // odd widths (the 365-wide linear mapping): element by element
         const int g1 = grid_for(rows * c);
@@ -382,6 +407,7 @@ extern "C" int sp_rescale_bias(const void* x, void* y, int64_t rows, int32_t c, 
 extern "C" int sp_scale_add_bwd(const void* dy, const void* a, const float* g, void* da, float* dg, float* partials, int64_t numel,
                                 int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(dy && a && g && da && dg && partials && numel % 4 == 0, "sp_scale_add_bwd: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_scale_add_bwd");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // <= 512 grid-striding blocks, one partial sum each (thousands of blocks ending in one same-address atomic serialised
     // there: 31 us for a 31 MB pass); the second kernel adds them in block order
@@ -398,6 +424,7 @@ extern "C" int sp_scale_add_bwd(const void* dy, const void* a, const float* g, v
 extern "C" int sp_permute_chw_hwc(const void* src, void* dst, int32_t batch, int32_t c, int32_t hw, int32_t to_hwc,
                                   int32_t dtype, sp_stream_t stream) {
     SP_CHECK_ARG(src && dst && batch > 0 && c > 0 && hw > 0, "sp_permute_chw_hwc: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_permute_chw_hwc");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int g = grid_for((long)batch * c * hw);
     SP_DT_SWITCH(dtype,
@@ -410,6 +437,7 @@ extern "C" int sp_permute_chw_hwc(const void* src, void* dst, int32_t batch, int
 extern "C" int sp_channel_sum(const void* x, int32_t ld, int64_t pixels, int32_t c, float* out, float* partials, int32_t dtype,
                               sp_stream_t stream) {
     SP_CHECK_ARG(x && out && partials && ld >= c && c > 0, "sp_channel_sum: bad args");
+    SP_CHECK_DTYPE(dtype, "sp_channel_sum");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int groups = (c + 3) / 4, lanes = groups < 256 ? groups : 256, pix_par = 256 / lanes;
     long blocks = pixels / ((long)pix_par * 32);

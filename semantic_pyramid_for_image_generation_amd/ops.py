@@ -1688,6 +1688,16 @@ def _float3(values):
     return None if values is None else ctypes.cast((ctypes.c_float * 3)(*values), ctypes.c_void_p)
 
 
+def _ingest_src_dtype(img: torch.Tensor, dtype) -> int:
+    """src_dtype of every ingest entry, plain and augmenting: the image's own type, which must be fp32 or the storage type itself.  The
+    two 16-bit types never mix: each compilation of the library decodes a 16-bit source as ITS 16-bit type (include/sempyr.h refuses the
+    mix with SP_ERR_UNSUPPORTED; this says which tensor it was)."""
+    if img.dtype != torch.float32 and img.dtype != dtype and is_16bit(img.dtype) and is_16bit(dtype):
+        raise L.SempyrError("the ingest takes an fp32 image or one of the storage type: a %s image cannot be ingested into %s storage "
+                            "(convert it first)" % (img.dtype, dtype))
+    return sp_dtype(img.dtype)
+
+
 class _IngestFn(torch.autograd.Function):
     """3-channel image (any strides; fp32 or compute dtype) -> NHWC with zero-padded channels, optional affine."""
 
@@ -1698,7 +1708,7 @@ class _IngestFn(torch.autograd.Function):
         cp = pad_channels(c, dtype)
         y = nhwc_empty(n, cp, h, w, dtype, img.device)
         sn, scs, sh, sw = img.stride()
-        L.call("sp_ingest_image", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, ptr(y), n, c, h, w, cp, _float3(scale3), _float3(shift3),
+        L.call("sp_ingest_image", ptr(img), _ingest_src_dtype(img, dtype), sn, scs, sh, sw, ptr(y), n, c, h, w, cp, _float3(scale3), _float3(shift3),
                sp_dtype(dtype), stream())
         ctx.cfg = (n, c, h, w, cp, scale3, img.dtype)
         return y
@@ -1732,7 +1742,7 @@ def ingest_image_pair(img_a: torch.Tensor, img_b: torch.Tensor, dtype, scale3=No
         sc, sf = _float3(scale3), _float3(shift3)
         for img, off in ((img_a.detach(), 0), (img_b.detach(), na)):
             sn, scs, sh, sw = img.stride()
-            L.call("sp_ingest_image", ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz),
+            L.call("sp_ingest_image", ptr(img), _ingest_src_dtype(img, dtype), sn, scs, sh, sw, ctypes.c_void_p(y.data_ptr() + off * h * w * cp * esz),
                    img.shape[0], c, h, w, cp, sc, sf, sp_dtype(dtype), stream())
     return y
 
@@ -2047,7 +2057,7 @@ def _augment_fwd(img, y_ptr, dtype, cp, u, policy, p=None, table=None, ctable=No
     sn, scs, sh, sw = img.stride()
     part = _augment_partials(n, h, w, policy, False, img.device, table is not None)
     name, extra = _augment_entry(False, p, table, part, ctable)
-    L.call(name, ptr(img), sp_dtype(img.dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, *extra, sp_dtype(dtype), stream())
+    L.call(name, ptr(img), _ingest_src_dtype(img, dtype), sn, scs, sh, sw, y_ptr, n, h, w, cp, ptr(u), policy, *extra, sp_dtype(dtype), stream())
 
 
 class _AugmentIngestFn(torch.autograd.Function):
