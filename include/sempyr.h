@@ -558,6 +558,29 @@ int sp_augment_ingest_bwd_gated(const void* dy, int32_t cp, void* dsrc, int32_t 
 int sp_ada_observe(const float* pred, int64_t numel, float threshold, void* state, sp_stream_t stream);
 int sp_ada_adjust(void* state, int32_t interval, float target, float step, sp_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * Adaptive pseudo augmentation (Jiang et al. 2021, "Deceive D", APA): with a probability p that lives in DEVICE memory, an image of
+ * the discriminator's real branch is replaced by a generated one that keeps the "real" label.  The reference has NO counterpart.
+ * csrc/apa.hip, DESIGN.md section 22.  ONE launch, pure data movement:
+ *   dst      contiguous fp32 n x 3 x h x w_
+ *   dst[i] = float(fake[i])  iff  w_u[i] < p_dev[0]   (strict, fp32 - the gate's compare above; a NaN p takes nothing)
+ *            float(real[i])  otherwise
+ * real / fake: 3-channel batches with the ELEMENT strides (rn, rc, rh, rw) / (fn, fc, fh, fw) of their n, c, h, w axes (any layout;
+ * strides >= 0), each of type real_dtype / fake_dtype: SP_F32 or the storage type `dtype`, under sp_ingest_image's rule - the two
+ * 16-bit types never mix: an SP_BF16 source under SP_F16 storage, and an SP_F16 source under SP_BF16 or SP_F32 storage, are
+ * SP_ERR_UNSUPPORTED and nothing is launched.  `dtype` chooses the compilation that decodes a 16-bit source, nothing else.
+ * A 16-bit value is widened exactly; an fp32 value passes bit for bit, NaN payloads and infinities included.
+ * w_u: n fp32 uniforms in device memory, one per image; p_dev: one fp32 value in device memory (&state[0] of the controller above,
+ * in an instance of its own).  Both are read when the kernel RUNS: no host value, grid size or address depends on them, and a captured
+ * graph follows p without a re-capture.  An image's choice is uniform over a block (grid: blocks x images), so a block reads only the
+ * source it chose.  No atomics, no reduction: two runs give the same bits.  dst must not overlap a source.
+ * Refused with SP_ERR_INVALID before any launch: a NULL real, fake, dst, w_u or p_dev; n, h or w_ < 1 (and n > 65535, h * w_ > 2^28);
+ * a dtype, real_dtype or fake_dtype that is no SP_F32 / SP_BF16 / SP_F16; a negative stride.
+ * ---------------------------------------------------------------------------------------------- */
+int sp_apa_select(const void* real, int32_t real_dtype, int64_t rn, int64_t rc, int64_t rh, int64_t rw,
+                  const void* fake, int32_t fake_dtype, int64_t fn, int64_t fc, int64_t fh, int64_t fw,
+                  float* dst, int32_t n, int32_t h, int32_t w_,
+                  const float* w_u, const float* p_dev, int32_t dtype, sp_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * Geometric augmentation inside the ingest pass (Karras et al. 2020, "ADA": pixel blitting and general geometric transforms): x-flip,
  * 90-degree rotations, isotropic scaling and arbitrary rotation compose with the translation above into ONE 2 x 3 affine map per image,
  * applied by bilinear resampling; the backward pass is the exact adjoint computed by GATHER (no float atomics, fixed summation order).

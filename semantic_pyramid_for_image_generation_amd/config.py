@@ -55,6 +55,10 @@ results beyond floating-point summation order.  The kernel library itself reads 
     lecam                 SP_LECAM               ""       LeCam regularization of the discriminator (ops.LeCam): weight or weight:decay or weight:decay:start
                                                           (decay 0.99 and start 1000 by default); empty / 0 = off: no launch, no allocation, no new result (part of the
                                                           training recipe, as augment is)
+    apa                   SP_APA                 ""       adaptive pseudo augmentation (Jiang et al. 2021; ops.apa_select, csrc/apa.hip): with probability p an
+                                                          image of the discriminator's real branch is a generated one that keeps the "real" label - a number in
+                                                          [0, 1] = fixed p; "adaptive" or "adaptive:<target>" = steered on the device as augment_p is, by a controller
+                                                          of its own; empty = off: no draw, no launch, no allocation, no checkpoint key (part of the training recipe)
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -145,6 +149,41 @@ def _checked_lecam(text) -> str:
     return text
 
 
+def parse_apa(spec):
+    """SP_APA / ModelWrapper(apa=...): None or "" = off (None); a number in [0, 1] (or its string) = ("fixed", p); "adaptive" or
+    "adaptive:<target>" with a target in [-1, 1] = ("adaptive", target), 0.6 where it is left out; anything else is an error."""
+    bad = ValueError("SP_APA takes a probability in [0, 1], 'adaptive' or 'adaptive:<target>' with a target in [-1, 1] (empty = off), got %r" % (spec,))
+    if spec is None:
+        return None
+    if isinstance(spec, bool) or not isinstance(spec, (int, float, str)):
+        raise bad
+    if isinstance(spec, str):
+        spec = spec.strip()
+        if spec == "":
+            return None
+        if spec == "adaptive":
+            return "adaptive", 0.6
+    try:
+        if isinstance(spec, str) and spec.startswith("adaptive:"):
+            target = float(spec[9:])
+            if not -1.0 <= target <= 1.0:
+                raise bad
+            return "adaptive", target
+        p = float(spec)
+    except ValueError:
+        raise bad from None
+    if not 0.0 <= p <= 1.0:
+        raise bad
+    return "fixed", p
+
+
+def _checked_apa(text) -> str:
+    """The SP_APA string as it is, after parse_apa has accepted it (a malformed value fails at import, as the other parsers do)."""
+    text = (text or "").strip()
+    parse_apa(text)
+    return text
+
+
 @dataclass
 class Config:
     direct_grads: bool = True
@@ -180,6 +219,7 @@ class Config:
     metrics: str = ""
     gan_loss: str = ""
     lecam: str = ""
+    apa: str = ""
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -199,7 +239,8 @@ class Config:
                    augment=os.environ.get("SP_AUGMENT", ""), augment_p=os.environ.get("SP_AUGMENT_P", "").strip(),
                    clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")),
                    metrics=",".join(parse_metrics(os.environ.get("SP_METRICS"))),
-                   gan_loss=parse_gan_loss(os.environ.get("SP_GAN_LOSS")), lecam=_checked_lecam(os.environ.get("SP_LECAM")))
+                   gan_loss=parse_gan_loss(os.environ.get("SP_GAN_LOSS")), lecam=_checked_lecam(os.environ.get("SP_LECAM")),
+                   apa=_checked_apa(os.environ.get("SP_APA")))
 
 
 CFG = Config.from_env()

@@ -38,6 +38,11 @@ And ``metrics`` (or SP_METRICS): besides the FID, ``evaluate()`` scores KID, pre
 Inception Score ("is": ``inception_score``, ``inception_score_std`` of the fake set over ``metrics_is_splits`` splits) from the
 same activations, kept on the device (metrics.py, csrc/metrics.hip, DESIGN.md sections 17 and 19); ``validate()`` still returns the FID, keeps
 the dict in ``last_metrics`` and ``train()`` logs its keys beside ``fid``.  Off by default: validate() is exactly what it was.
+And ``apa`` (or SP_APA): adaptive pseudo augmentation (Jiang et al. 2021, "Deceive D") - with probability p an image
+of the discriminator's REAL branch is replaced by a generated one that keeps the "real" label (ops.apa_select: one launch in front of
+whatever module D is, from one more (B,) draw of uniforms behind the augmentation's and in front of the latents); a fixed p, or one
+steered as augment_p is, by a second ops.AdaptiveAugment with its own state; the generator, the VGG-16 and the whole G step keep the true
+real images.  It needs neither ``augment`` nor this package's Discriminator.  Off by default: no draw, no launch, no allocation, no key.
 """
 from __future__ import annotations
 
@@ -80,7 +85,8 @@ class ModelWrapper(object):
                  augment_p=None,
                  metrics=None,
                  gan_loss=None,
-                 lecam=None) -> None:
+                 lecam=None,
+                 apa=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -161,6 +167,10 @@ class ModelWrapper(object):
         # allocated HERE, outside any graph's pool.  _lecam_reg: the regularizer of the last eager discriminator phase.
         self._lecam = self._make_lecam(CFG.lecam if lecam is None else lecam, parse_lecam)
         self._lecam_reg = None
+        # apa: adaptive pseudo augmentation - None: CFG.apa (SP_APA); "" = off: nothing below exists.  A number in
+        # [0, 1]: fixed p.  "adaptive" / "adaptive:<target>" or an ops.AdaptiveAugment: steered on the device, by a controller of its own
+        # beside augment_p's.  _apa owns the device state; it is allocated HERE, outside any graph's pool.
+        self._apa = self._make_apa(CFG.apa if apa is None else apa)
         # metrics: what validate() / evaluate() score besides the FID - a comma-separated subset of kid, prdc, is (metrics.py, DESIGN.md
         # sections 17, 19); None: CFG.metrics (SP_METRICS); "" = off: validate() is exactly what it is without.  An unknown word is an error
         # here.  metrics_nearest_k: the k of the precision / recall / density / coverage radii; metrics_is_splits: the splits of the
@@ -354,6 +364,30 @@ class ModelWrapper(object):
         self.logger.hyperparameter['augment_p'] = str(dict(ada.settings(), p=float(ada.p)) if not ada.adaptive else ada.settings())
         return ada
 
+    def _make_apa(self, spec):
+        """The constructor's apa -> an ops.AdaptiveAugment (fixed or adaptive) or None (off).  The controller is ops.AdaptiveAugment as it
+        stands, in an instance of its own; its threshold is the D loss module's decision_threshold, as augment_p takes it."""
+        from .config import parse_apa
+        if isinstance(spec, ops.AdaptiveAugment):
+            apa = spec
+        else:
+            try:
+                fields = parse_apa(spec)
+            except ValueError:
+                raise ops.L.SempyrError("apa takes a probability in [0, 1], 'adaptive', 'adaptive:<target>' or an ops.AdaptiveAugment "
+                                        "(got %r)" % (spec,)) from None
+            if fields is None:
+                return None
+            device = next(self.discriminator.parameters()).device
+            if device.type != "cuda":
+                raise ops.L.SempyrError("apa: the probability's state lives on the discriminator's GPU; move the discriminator there first")
+            if fields[0] == "adaptive":
+                apa = ops.AdaptiveAugment(device, target=fields[1], threshold=float(getattr(self.discriminator_loss, "decision_threshold", 0.5)))
+            else:
+                apa = ops.AdaptiveAugment(device, p=fields[1], adaptive=False)
+        self.logger.hyperparameter['apa'] = str(dict(apa.settings(), p=float(apa.p)) if not apa.adaptive else apa.settings())
+        return apa
+
     def _make_lecam(self, spec, parse):
         """The constructor's lecam -> an ops.LeCam or None (off)."""
         if isinstance(spec, ops.LeCam):
@@ -392,6 +426,17 @@ class ModelWrapper(object):
             return out
         out = dict(out)
         out["augment_p"], out["augment_rt"] = self._ada.p.reshape(()), self._ada.r.reshape(())
+        return out
+
+    def _apa_adaptive(self) -> bool:
+        return self._apa is not None and self._apa.adaptive
+
+    def _with_apa(self, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The step's results plus, with APA's adaptive controller on ONLY, its p and r_t: views of its device state, as augment_p's are."""
+        if not self._apa_adaptive():
+            return out
+        out = dict(out)
+        out["apa_p"], out["apa_rt"] = self._apa.p.reshape(()), self._apa.r.reshape(())
         return out
 
     def _with_grad_norms(self, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -442,6 +487,32 @@ class ModelWrapper(object):
         return self._uniform_rows(images_real, augment_z, 8, self._aug_cmat, "augment_z",
                                   "has no color-matrix augmentation (brightness / contrast / lumaflip / hue / saturation in augment / SP_AUGMENT)")
 
+    def _apa_rows(self, images_real, apa_w):
+        """The step's (B,) uniforms of the pseudo augmentation, one per image of D's real branch - drawn here unless the caller brings
+        them, or None with APA off (then bringing them raises).  Drawn right behind the augmentation's draws (first where there are none)
+        and in front of the latents."""
+        if self._apa is None:
+            if apa_w is not None:
+                raise ops.L.SempyrError("apa_w given, but this ModelWrapper has no pseudo augmentation (apa / SP_APA)")
+            return None
+        shape = (images_real.shape[0],)
+        if apa_w is None:
+            return torch.rand(shape, dtype=torch.float32, device=images_real.device)
+        if tuple(apa_w.shape) != shape:
+            raise ops.L.SempyrError("apa_w must be %s (one uniform per image), got %s" % (shape, tuple(apa_w.shape)))
+        return apa_w.detach().to(device=images_real.device, dtype=torch.float32).contiguous()
+
+    def _apa_images(self, images_real, images_fake, apa_w, out=None):
+        """What D's real branch sees with APA on: image i is the pseudo source's iff apa_w[i] < p, else the real one (ops.apa_select, one
+        launch, into `out` - the graphs' static buffer - if given).  THE PSEUDO SOURCE, one rule: the fake images of the generator step
+        where the discriminator phase's pair forward has made them (self._fake_ahead: fresh latents, the same labels, features and masks -
+        what the official implementation draws at extra cost), detached; else the D step's own fake images.  Row i pairs with label i
+        either way."""
+        pseudo = self._fake_ahead[0] if self._fake_ahead is not None else images_fake
+        if tuple(pseudo.shape) != tuple(images_real.shape):
+            raise ops.L.SempyrError("apa: the generated images %s do not have the real images' shape %s" % (tuple(pseudo.shape), tuple(images_real.shape)))
+        return ops.apa_select(images_real, pseudo.detach(), apa_w, self._apa.p, out=out)
+
     def _augment_ctables(self, images_real, aug_z, out=None):
         """The step's (3, B, 12) color matrices: all 3B rows in ONE decode launch (into `out`, the graphs' static buffer, if given) - or
         None without color-matrix words."""
@@ -476,14 +547,16 @@ class ModelWrapper(object):
             D._augment_p = None
 
     def _d_phase(self, images_real, labels, labels_f, masks, noise_d, features_real=None, noise_g=None, aug_u=None, aug_v=None,
-                 aug_t_out=None, aug_z=None, aug_c_out=None):
+                 aug_t_out=None, aug_z=None, aug_c_out=None, apa_w=None, apa_out=None):
         """model_wrapper.py:136-160: forward passes and backward of the discriminator step (everything but Adam).  features_real: the
         pyramid of images_real where an earlier generator step has already computed it (_g_rest, next_images_real).  noise_g: the
         latents of the generator step, for the case that its forward is taken in the same pass as this step's (_g_pair_ok).  aug_u: the
         step's uniforms (_augment_rows) - D sees T(real; aug_u[0]) and T(fake; aug_u[1]); the generator and the VGG-16 see the images.
         aug_v: the uniforms of the geometric words (_augment_geom_rows); their tables are decoded HERE - one launch, inside the first
         captured graph - into aug_t_out (or a fresh tensor) and left in self._aug_tables for the generator step.  aug_z: the uniforms of the
-        color-matrix words (_augment_cmat_rows), decoded likewise into aug_c_out and left in self._aug_ctables."""
+        color-matrix words (_augment_cmat_rows), decoded likewise into aug_c_out and left in self._aug_ctables.  apa_w: the uniforms of the
+        pseudo augmentation (_apa_rows) - D's real branch then sees _apa_images(...) (into apa_out or a fresh tensor) in place of
+        images_real; the VGG-16, the generator's conditioning and everything behind this phase keep images_real."""
         G, D, V = self.generator, self.discriminator, self.vgg16
         aug_t = self._aug_tables = self._augment_tables(images_real, aug_u, aug_v, aug_t_out)
         aug_c = self._aug_ctables = self._augment_ctables(images_real, aug_z, aug_c_out)
@@ -505,13 +578,15 @@ class ModelWrapper(object):
             if hasattr(G, "map_mode"):
                 G.map_mode = "stash"                  # this forward and the G step's see the same pyramid, masks and weights
             images_fake = G(input=noise_d, features=features_real, masks=masks, class_id=labels_f)
+        # one launch behind the generator's forward(s) and in front of D (inside the first captured graph)
+        images_for_d = images_real if apa_w is None else self._apa_images(images_real, images_fake, apa_w, apa_out)
         if CFG.d_pair and hasattr(D, "forward_pair") and D.training and images_fake.shape == images_real.shape:
             rows = None if aug_u is None else (aug_u[0], aug_u[1])
-            prediction_real, prediction_fake = self._d_call(D.forward_pair, rows, images_real, images_fake, labels,
+            prediction_real, prediction_fake = self._d_call(D.forward_pair, rows, images_for_d, images_fake, labels,
                                                             tables=None if aug_t is None else (aug_t[0], aug_t[1]),
                                                             ctables=None if aug_c is None else (aug_c[0], aug_c[1]))     # one trunk pass over 2B images
         else:
-            prediction_real = self._d_call(D, None if aug_u is None else (aug_u[0],), images_real, labels,
+            prediction_real = self._d_call(D, None if aug_u is None else (aug_u[0],), images_for_d, labels,
                                            tables=None if aug_t is None else (aug_t[0],), ctables=None if aug_c is None else (aug_c[0],))
             prediction_fake = self._d_call(D, None if aug_u is None else (aug_u[1],), images_fake, labels,
                                            tables=None if aug_t is None else (aug_t[1],), ctables=None if aug_c is None else (aug_c[1],))
@@ -519,6 +594,9 @@ class ModelWrapper(object):
             # the overfitting signal's counts (sp_ada_observe): one launch on D's fp32 predictions, inside the first captured graph; p
             # itself moves only behind Adam(G) (train_step), so every gate of this step reads the same value
             self._ada.observe(prediction_real)
+        if self._apa_adaptive():
+            # APA's own counts, right behind: over the whole real branch, replaced rows included (the official implementation's choice)
+            self._apa.observe(prediction_real)
         terms = []
         if self._lecam is not None:
             # one launch right behind it, inside the first captured graph too: means, anchors and the regularizer, whatever loss module
@@ -634,11 +712,13 @@ class ModelWrapper(object):
     def train_step(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1,
                    noise_d: Optional[torch.Tensor] = None, noise_g: Optional[torch.Tensor] = None,
                    next_images_real: Optional[torch.Tensor] = None, augment_u: Optional[torch.Tensor] = None,
-                   augment_v: Optional[torch.Tensor] = None, augment_z: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   augment_v: Optional[torch.Tensor] = None, augment_z: Optional[torch.Tensor] = None,
+                   apa_w: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """One iteration of model_wrapper.py:131-190 on tensors already on the device.  ``noise_d`` / ``noise_g``
         replace the two ``torch.randn`` draws (model_wrapper.py:147,168) for parity runs, ``augment_u`` ((3, B, 8), with augmentation
         on only) the ``torch.rand`` draw in front of them, ``augment_v`` ((3, B, 4), with geometric words only) the one right behind
-        it, ``augment_z`` ((3, B, 8), with color-matrix words only) the one behind that.  Returns the loss scalars as device tensors (no host sync).
+        it, ``augment_z`` ((3, B, 8), with color-matrix words only) the one behind that, ``apa_w`` ((B,), with APA on only) the one behind
+        those and in front of the latents.  Returns the loss scalars as device tensors (no host sync).
 
         ``next_images_real`` (optional): the real images of the NEXT call (the same tensor object must then be passed as its
         ``images_real``).  The frozen VGG-16 sees them in the pass it makes over this iteration's fake images - one pass over 2B
@@ -658,9 +738,11 @@ class ModelWrapper(object):
         aug_u = self._augment_rows(images_real, augment_u)
         aug_v = self._augment_geom_rows(images_real, augment_v)
         aug_z = self._augment_cmat_rows(images_real, augment_z)
+        apa_w = self._apa_rows(images_real, apa_w)
         with profiling.range("D phase"):
             features_real, loss_d_real, loss_d_fake = self._d_phase(images_real, labels, labels_f, masks, noise_d,
-                                                                      self._features_ahead(images_real), noise_g, aug_u, aug_v, aug_z=aug_z)
+                                                                      self._features_ahead(images_real), noise_g, aug_u, aug_v, aug_z=aug_z,
+                                                                      apa_w=apa_w)
             self._start_reduce("d", self._d_params, eager=True)
         with profiling.range("G forward"):
             images_fake, noise_g = self._g_forward(images_real, labels_f, masks, features_real, noise_g)
@@ -677,11 +759,13 @@ class ModelWrapper(object):
             self._optimizer_step("g", self.generator_optimizer)
             if self._adaptive():
                 self._ada.adjust(images_real.shape[0])
+            if self._apa_adaptive():
+                self._apa.adjust(images_real.shape[0])
         self.iterations += 1
         out = self._with_augment_p(self._with_grad_norms({"loss_discriminator_real": loss_d_real.detach(), "loss_discriminator_fake": loss_d_fake.detach(),
                                      "loss_generator": loss_g.detach(), "loss_generator_semantic_reconstruction": loss_rec.detach().reshape(()),
                                      "loss_generator_diversity": loss_div.detach(), "images_fake": images_fake.detach()}))
-        return self._with_lecam(out, self._lecam_reg)
+        return self._with_apa(self._with_lecam(out, self._lecam_reg))
 
     # ------------------------------------------------------------------------------------------
     def capture_graphs(self, images_real: torch.Tensor, labels: torch.Tensor, masks, w_rec: float = 0.1, w_div: float = 0.1) -> None:
@@ -719,6 +803,9 @@ class ModelWrapper(object):
         # and the uniforms of the color-matrix words with the matrices the first graph's second decode launch writes
         st["augment_z"] = torch.zeros((3, zdim[0], 8), dtype=torch.float32, device=images_real.device) if self._aug_cmat else None
         st["augment_c"] = torch.zeros((3 * zdim[0], 12), dtype=torch.float32, device=images_real.device) if self._aug_cmat else None
+        # and the uniforms of the pseudo augmentation with the batch D's real branch reads (None with APA off: no buffer, no draw)
+        st["apa_w"] = torch.zeros((zdim[0],), dtype=torch.float32, device=images_real.device) if self._apa is not None else None
+        st["apa_images"] = torch.zeros_like(images_real, dtype=torch.float32, memory_format=torch.contiguous_format) if self._apa is not None else None
         # The pyramid of the real images is computed AHEAD (config.CFG.vgg_pair): the generator-step graph takes the next batch's real
         # images (st["images_next"]) through the VGG pass it makes over the fake images and leaves their features in st["feats_real"],
         # which the discriminator-step graph of the next replay reads.  Eager once here, so that the first replay finds them.
@@ -747,7 +834,8 @@ class ModelWrapper(object):
                 lab_d = cls if isinstance(self.discriminator, Discriminator) else st["labels"]      # (a caller's own module gets what it was written for)
                 lab_g = cls if isinstance(self.generator, Generator) else st["labels"]
                 feats, l_real, l_fake = self._d_phase(st["images"], lab_d, lab_g, st["masks"], st["noise_d"], st["feats_real"], st["noise_g"],
-                                                      st["augment_u"], st["augment_v"], st["augment_t"], st["augment_z"], st["augment_c"])
+                                                      st["augment_u"], st["augment_v"], st["augment_t"], st["augment_z"], st["augment_c"],
+                                                      st["apa_w"], st["apa_images"])
             st["lecam_reg"] = self._lecam_reg                      # (None with LeCam off) the first graph's static output
             st["d_grads"] = [p.grad for p in self._d_params]
             # second graph: what the generator step can do in front of the discriminator's optimizer step - its forward, unless that rode
@@ -794,7 +882,8 @@ class ModelWrapper(object):
     def train_step_graphed(self, images_real: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, masks=None,
                            noise_d: Optional[torch.Tensor] = None, noise_g: Optional[torch.Tensor] = None,
                            next_images_real: Optional[torch.Tensor] = None, augment_u: Optional[torch.Tensor] = None,
-                           augment_v: Optional[torch.Tensor] = None, augment_z: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                           augment_v: Optional[torch.Tensor] = None, augment_z: Optional[torch.Tensor] = None,
+                           apa_w: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """train_step() through the captured graphs (capture_graphs() first).  images / labels / masks: new batch to copy into
         the graphs' static inputs, or None to reuse the resident one.  next_images_real: as in train_step() - the next call's real
         images, whose VGG pyramid this call computes ahead; without it (and outside the resident mode) the next call computes its
@@ -823,6 +912,12 @@ class ModelWrapper(object):
             st["augment_z"].uniform_()                          # behind the draws above and in front of the latents, as train_step() draws
         else:
             st["augment_z"].copy_(self._augment_cmat_rows(st["images"], augment_z))
+        if st.get("apa_w") is None:
+            self._apa_rows(st["images"], apa_w)                 # (APA off: raises if the caller brings uniforms)
+        elif apa_w is None:
+            st["apa_w"].uniform_()                              # behind the augmentation's draws and in front of the latents, as train_step() draws
+        else:
+            st["apa_w"].copy_(self._apa_rows(st["images"], apa_w))
         if noise_d is None:
             st["noise_d"].normal_()
         else:
@@ -890,8 +985,10 @@ class ModelWrapper(object):
             self._optimizer_step("g", self.generator_optimizer)
             if self._adaptive():
                 self._ada.adjust(st["images"].shape[0])             # eager, as the optimizer steps: p moves between replays
+            if self._apa_adaptive():
+                self._apa.adjust(st["images"].shape[0])
         self.iterations += 1
-        return self._with_lecam(self._with_augment_p(self._with_grad_norms(st["out"])), st.get("lecam_reg"))
+        return self._with_apa(self._with_lecam(self._with_augment_p(self._with_grad_norms(st["out"])), st.get("lecam_reg")))
 
     # ------------------------------------------------------------------------------------------
     def _batch_signature(self, images_real, labels, masks):
@@ -1009,6 +1106,8 @@ class ModelWrapper(object):
             names += ("augment_p", "augment_rt")
         if self._lecam is not None:                             # ... and the regularizer with its two anchors
             names += ("loss_discriminator_lecam", "lecam_anchor_real", "lecam_anchor_fake")
+        if self._apa_adaptive():                                # ... and the pseudo augmentation's probability and signal
+            names += ("apa_p", "apa_rt")
         for epoch in range(epochs):
             self.generator.train()
             self.discriminator.train()
@@ -1056,6 +1155,8 @@ class ModelWrapper(object):
                     checkpoint["augment_state"] = self._ada.state_dict()
                 if self._lecam is not None:
                     checkpoint["lecam_state"] = self._lecam.state_dict()
+                if self._apa_adaptive():
+                    checkpoint["apa_state"] = self._apa.state_dict()
                 torch.save(checkpoint,
                            os.path.join(self.path_save_models, 'checkpoint_{}.pt'.format(str(epoch).zfill(3))))
             self.inference(device=device)
@@ -1087,6 +1188,18 @@ class ModelWrapper(object):
                 raise ops.L.SempyrError("load_augment_state(): neither an AdaptiveAugment state nor a checkpoint with an 'augment_state' key")
             state = state["augment_state"]
         self._ada.load_state_dict(state)
+
+    def load_apa_state(self, checkpoint_or_state) -> None:
+        """Restores the pseudo augmentation's controller for a resumed run: a checkpoint of train() (its "apa_state" key) or an
+        AdaptiveAugment.state_dict().  The device state is written in place: captured graphs stay valid."""
+        if not self._apa_adaptive():
+            raise ops.L.SempyrError("load_apa_state(): this ModelWrapper steers no pseudo-augmentation probability (apa / SP_APA)")
+        state = checkpoint_or_state
+        if "state" not in state:
+            if "apa_state" not in state:
+                raise ops.L.SempyrError("load_apa_state(): neither an AdaptiveAugment state nor a checkpoint with an 'apa_state' key")
+            state = state["apa_state"]
+        self._apa.load_state_dict(state)
 
     def load_lecam_state(self, checkpoint_or_state) -> None:
         """Restores the LeCam anchors for a resumed run: a checkpoint of train() (its "lecam_state" key) or an ops.LeCam.state_dict().

@@ -2216,6 +2216,41 @@ class AdaptiveAugment:
         self.state.copy_(state)
 
 
+def apa_select(real: torch.Tensor, fake: torch.Tensor, w_u: torch.Tensor, p: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adaptive pseudo augmentation's selection (Jiang et al. 2021; include/sempyr.h: sp_apa_select), ONE launch: a
+    contiguous fp32 (n, 3, h, w) batch whose image i is fake[i] iff w_u[i] < p (strict, fp32), else real[i] - 16-bit values widened
+    exactly, fp32 values bit for bit.  real / fake: 3-channel batches of one shape on the GPU, any strides, each fp32 or a 16-bit type
+    (the two 16-bit types never mix: the storage type of the call is the 16-bit type among them).  w_u: (n,) fp32 uniforms on that
+    device; p: the 1-element fp32 device tensor of the gate (_augment_gate; AdaptiveAugment.p is one), read when the kernel runs.
+    out: the result's buffer (the graphs' static one), else a fresh tensor.  Runs under no_grad: the result carries no autograd graph -
+    APA feeds detached images to D."""
+    with torch.no_grad():
+        real, fake = real.detach(), fake.detach()
+        require_gpu(real)
+        if real.dim() != 4 or real.shape[1] != 3 or tuple(fake.shape) != tuple(real.shape) or fake.device != real.device:
+            raise L.SempyrError("apa_select takes two 3-channel batches (n, 3, h, w) of one shape on one GPU, got %s and %s"
+                                % (tuple(real.shape), tuple(fake.shape)))
+        p = _augment_gate(p, real.device)
+        if p is None:
+            raise L.SempyrError("apa_select takes p as a 1-element fp32 tensor on the images' GPU (got None)")
+        n, _, h, w = real.shape
+        if not (isinstance(w_u, torch.Tensor) and w_u.device == real.device and w_u.dtype == torch.float32 and tuple(w_u.shape) == (n,)
+                and w_u.is_contiguous()):
+            raise L.SempyrError("apa_select takes w_u as a contiguous fp32 (n,) tensor on the images' GPU, one uniform per image (got %r for "
+                                "%d images)" % (((tuple(w_u.shape), w_u.dtype, str(w_u.device)) if isinstance(w_u, torch.Tensor) else w_u), n))
+        # the storage type: the 16-bit type among the sources (fp32 without one); _ingest_src_dtype refuses the other 16-bit type
+        dtype = real.dtype if is_16bit(real.dtype) else (fake.dtype if is_16bit(fake.dtype) else torch.float32)
+        dt_real, dt_fake = _ingest_src_dtype(real, dtype), _ingest_src_dtype(fake, dtype)
+        if out is None:
+            out = torch.empty((n, 3, h, w), dtype=torch.float32, device=real.device)
+        elif not (out.device == real.device and out.dtype == torch.float32 and tuple(out.shape) == (n, 3, h, w) and out.is_contiguous()):
+            raise L.SempyrError("apa_select: out must be a contiguous fp32 %s tensor on the images' GPU (got %s %s)"
+                                % ((n, 3, h, w), tuple(out.shape), out.dtype))
+        L.call("sp_apa_select", ptr(real), dt_real, *real.stride(), ptr(fake), dt_fake, *fake.stride(), ptr(out), n, h, w, ptr(w_u), ptr(p),
+               sp_dtype(dtype), stream())
+    return out
+
+
 def mask_concat(feat: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """cat(feat * mask, mask) with the channel count padded to a 16-byte multiple (models.py:94).  No autograd:
     the features come from the frozen VGG under no_grad and mask gradients are dead."""
