@@ -90,12 +90,18 @@ int sp_version(void);
  *   SP_TUNE_CONV_PP_PRIO     bit 0: s_setprio 1 around every MFMA segment of the ping-pong kernel (default 1); bit 1: static priority 1
  *                            for the second-dispatched half of the block
  *   SP_TUNE_PAIRSET_SEGMENTS the pair-set kernels (sp_pairset_knn / _cover) cut the column blocks of a row block into this many segments
- *                            (default: what gives 6144 blocks; always clamped to [1, column blocks]); sp_pairset_workspace follows it */
+ *                            (default: what gives 6144 blocks; always clamped to [1, column blocks]); sp_pairset_workspace follows it
+ *   SP_TUNE_ATTN_PIECES      the 16-bit MFMA attention kernels give an image this many blocks, each walking ceil(nqb / pieces) of its
+ *                            nqb = ceil(n / 64) query blocks (default: one query block each where batch x nqb blocks find a slot on
+ *                            the chip, otherwise the shortest walk that brings them down to one round; clamped to [1, nqb]);
+ *                            sp_attention_plan says what a launch gets.  4096 (diagnostics, tools/time_attention.py --phases):
+ *                            sp_attention_bwd launches the TIMING build of its one-slab-per-query-block kernel and no reduce -
+ *                            the slabs then hold cycle counts per phase and dk / dv are not written */
 enum { SP_TUNE_CONV_TALL = 0, SP_TUNE_IGEMM_DMA = 1, SP_TUNE_WGRAD_ROWS = 2, SP_TUNE_DETERMINISTIC = 3,
        SP_TUNE_SPLITK_TARGET = 4, SP_TUNE_SPLITK_MINSTEPS = 5, SP_TUNE_CONV1X1_DIRECT = 6, SP_TUNE_CONV_SHORT = 7,
        SP_TUNE_WGRAD9_BLOCKS = 8, SP_TUNE_WGRAD_BLOCKS = 9, SP_TUNE_WGRAD_MINSTEPS = 10, SP_TUNE_WGRAD_SMALL_M = 11,
        SP_TUNE_WGRAD_K1_TILE64 = 12, SP_TUNE_WGRAD_ROWS_THIN = 13, SP_TUNE_WGRAD_ROWS_BLOCKS = 14, SP_TUNE_WGRAD_ROWS_SLABS = 15,
-       SP_TUNE_CONV_STAGGER = 16, SP_TUNE_CONV1X1_SPLITK = 17, SP_TUNE_WGRAD1X1 = 18, SP_TUNE_CONV_CIN8 = 19, SP_TUNE_CONV_THINCO = 20, SP_TUNE_CONV_PP = 21, SP_TUNE_CONV_PP_PRIO = 22, SP_TUNE_WGRAD_PP = 23, SP_TUNE_BN_ITERS = 24, SP_TUNE_IGEMM_TILE = 25, SP_TUNE_CONV_PPW = 26, SP_TUNE_LINEAR_KS = 27, SP_TUNE_CONV_PP_SPLIT = 28, SP_TUNE_PAIRSET_SEGMENTS = 29, SP_TUNE_COUNT = 30 };
+       SP_TUNE_CONV_STAGGER = 16, SP_TUNE_CONV1X1_SPLITK = 17, SP_TUNE_WGRAD1X1 = 18, SP_TUNE_CONV_CIN8 = 19, SP_TUNE_CONV_THINCO = 20, SP_TUNE_CONV_PP = 21, SP_TUNE_CONV_PP_PRIO = 22, SP_TUNE_WGRAD_PP = 23, SP_TUNE_BN_ITERS = 24, SP_TUNE_IGEMM_TILE = 25, SP_TUNE_CONV_PPW = 26, SP_TUNE_LINEAR_KS = 27, SP_TUNE_CONV_PP_SPLIT = 28, SP_TUNE_PAIRSET_SEGMENTS = 29, SP_TUNE_ATTN_PIECES = 30, SP_TUNE_COUNT = 31 };
 int sp_set_tuning(int32_t key, int32_t value);
 const char* sp_last_error_string(void);
 /* Name of the kernel (route) the last sp_conv2d_igemm / sp_conv2d_wgrad* call of THIS thread launched ("" before the first one):
@@ -456,7 +462,10 @@ int sp_upsample2_bwd(const void* dy, void* dx, int32_t n, int32_t h, int32_t w_,
  * 1/sqrt(d) scale.  q [b][n][d], k [b][nk][d], v [b][nk][dv], o [b][n][dv]; lse [b][n] fp32 saved for backward.
  * Backward: dk_f32 / dv_f32 are fp32 scratch of sp_attention_bwd_slabs() slabs of [b][nk][d] resp. [b][nk][dv] floats (one
  * partial sum per query block - 64 queries on the bf16 MFMA path, 32 or 16 on the fp32 path - added in block order by the
- * call: no atomics, no initialisation needed); dk / dv receive the result.
+ * call: no atomics, no initialisation needed); dk / dv receive the result.  Where K and V fit the LDS next to the block's tiles
+ * the MFMA backward sums the query blocks a block walks in registers and uses only the first sp_attention_plan() slabs; it
+ * neither writes nor reads the rest.  The walk follows the batch, so an image's dk / dv may differ in the last fp32 bits
+ * between batch sizes; the same call gives the same bits every time.
  * ---------------------------------------------------------------------------------------------- */
 int sp_attention_bwd_slabs(int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dtype, int64_t* slabs_out);
 int sp_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int32_t batch, int32_t n,
@@ -468,6 +477,12 @@ int sp_attention_bwd(const void* q, const void* k, const void* v, const void* do
  * "valu tq32" or "valu tq16" (the VALU kernels in their 32- and 16-query forms).  Same extent checks as the launchers, the same
  * predicates as their dispatch; host-only like sp_conv2d_route: touches no device state, callable without a GPU. */
 int sp_attention_route(int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dtype, const char** fwd, const char** bwd);
+/* The walk of the MFMA kernels for a launch of `batch` images on a device of `cus` compute units (cus <= 0: the current device's,
+ * read once): *fwd_walk / *bwd_walk = consecutive 64-query blocks one block walks (0: the forward is not on the MFMA kernel / the
+ * backward is not on its K/V-resident form), *bwd_slabs = the slabs of the scratch the backward writes and adds.  A pure
+ * function of its arguments and SP_TUNE_ATTN_PIECES; host-only with cus > 0. */
+int sp_attention_plan(int32_t batch, int32_t n, int32_t nk, int32_t d, int32_t dv, int32_t dtype, int32_t cus,
+                      int32_t* fwd_walk, int32_t* bwd_walk, int32_t* bwd_slabs);
 
 /* ------------------------------------------------------------------------------------------------
  * Glue: image ingest (NCHW/NHWC 3-channel source -> padded NHWC, optional affine = kornia.normalize at
