@@ -1036,6 +1036,44 @@ int sp_pairset_softmax_colsum(const float* a, int32_t n, int32_t lda, const floa
                               int32_t d, const double* lse, const double* h, int32_t splits, double* colsum, double* kl,
                               void* workspace, int64_t workspace_bytes, sp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Reconstruction fidelity of an image pair (reconstruction.hip): the sufficient statistics of PSNR, SSIM (Wang, Bovik,
+ * Sheikh, Simoncelli 2004, "Image Quality Assessment: From Error Visibility to Structural Similarity") and MS-SSIM (Wang, Simoncelli,
+ * Bovik 2003, "Multi-scale Structural Similarity for Image Quality Assessment").  The reference has NO counterpart.
+ * x, y: images [n][c][h][w_] addressed by the ELEMENT strides of their n, c, h, w axes (any layout, strides >= 0), each with its own
+ * dtype SP_F32 / SP_BF16 / SP_F16; a 16-bit value is widened exactly (by bit pattern: the file is compiled once), arithmetic is fp32.
+ *   window   g[k] = fp32(exp(-(k - 5)^2 / 4.5) / Z), k = 0..10, Z the float64 sum of the eleven exponentials; 2-D window g (x) g
+ *            (11 x 11, sigma 1.5), VALID positions only: (H_j - 10) x (W_j - 10) at scale j, no padding
+ *   moments  mx, my, exx, eyy, exy = windowed means of x, y, x^2, y^2, x y (horizontal 11 taps, then vertical 11 taps, fp32 fma);
+ *            sxx = exx - mx^2, syy = eyy - my^2, sxy = exy - mx my (population form, no 121 / 120)
+ *   maps     C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range:   cs = (2 sxy + C2) / (sxx + syy + C2),
+ *            l = (2 mx my + C1) / (mx^2 + my^2 + C1),   ssim = l cs
+ *   ssim_mean[n][c][j], cs_mean[n][c][j]   float64 means of the two maps over the valid positions of scale j
+ *   next scale   X_{j+1}[p][q] = ((X_j[2p][2q] + X_j[2p][2q+1]) + (X_j[2p+1][2q] + X_j[2p+1][2q+1])) * 0.25 in fp32
+ *   sqerr[n][c]  float64 sum over the plane of (double)d * (double)d, d = x - y in fp32 on the widened values
+ * scales in [1, 5]; h and w_ divisible by 2^(scales-1) with h >> (scales-1) and w_ >> (scales-1) >= 11 (refused, never padded).
+ * A NaN or an infinity in a plane of x or y (or a difference / moment that overflows fp32) makes the outputs of THAT (n, c) NaN and
+ * touches no other plane.  One launch per scale (a block owns a 16 x 32 tile of positions of one plane, stages the tile and its
+ * 10-pixel halo of both images in LDS, and writes the 2 x 2-pooled pixels it owns for the next scale) and one that adds the blocks'
+ * float64 partial sums in index order: no float atomics, every output bit-identical from launch to launch, nothing read outside the
+ * planes, no host synchronisation.  Any output pointer may be NULL.
+ * Refused with SP_ERR_INVALID and a message before any launch: a NULL x, y or workspace; workspace_bytes below sp_ssim_workspace();
+ * a dtype that is no SP_F32 / SP_BF16 / SP_F16; a negative stride; n, c, h, w_ < 1, n * c > 2^24, h or w_ > 32768, more than
+ * 2^31 - 1 tiles, scales outside [1, 5] or the divisibility / minimum-size rule; a data_range that is not finite or <= 0.
+ *
+ * sp_ssim_workspace: host logic only (callable without a GPU).  With P = n c, H_j = h >> j, W_j = w_ >> j and
+ * T_j = ceil((H_j - 10) / 16) ceil((W_j - 10) / 32) tiles per plane,
+ *   bytes = sum_{j=1}^{scales-1} 2 round8(4 P H_j W_j)  +  8 P (T_0 + 2 sum_{j=0}^{scales-1} T_j)
+ * laid out in that order: for j = 1 .. scales-1 the pooled fp32 planes [P][H_j][W_j] of x, then of y; then per scale the float64
+ * partial sums [P][T_j] of ssim, then of cs; then [P][T_0] of the squared error.  The workspace must be 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int sp_ssim_workspace(int32_t n, int32_t c, int32_t h, int32_t w_, int32_t scales, int64_t* bytes);
+int sp_ssim_stats(const void* x, int32_t x_dtype, int64_t xn, int64_t xc, int64_t xh, int64_t xw,
+                  const void* y, int32_t y_dtype, int64_t yn, int64_t yc, int64_t yh, int64_t yw,
+                  int32_t n, int32_t c, int32_t h, int32_t w_, int32_t scales, double data_range,
+                  double* ssim_mean, double* cs_mean, double* sqerr,
+                  void* workspace, int64_t workspace_bytes, sp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

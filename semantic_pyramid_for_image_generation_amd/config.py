@@ -59,6 +59,12 @@ results beyond floating-point summation order.  The kernel library itself reads 
                                                           image of the discriminator's real branch is a generated one that keeps the "real" label - a number in
                                                           [0, 1] = fixed p; "adaptive" or "adaptive:<target>" = steered on the device as augment_p is, by a controller
                                                           of its own; empty = off: no draw, no launch, no allocation, no checkpoint key (part of the training recipe)
+    reconstruction        SP_RECONSTRUCTION      ""       per-level reconstruction fidelity ModelWrapper.evaluate_reconstruction() scores (reconstruction.py,
+                                                          csrc/reconstruction.hip): a comma-separated subset of psnr, ssim, ms_ssim, each image
+                                                          against its own inversion from every level of reconstruction_levels; empty = off: no launch, no
+                                                          allocation, no draw, {} returned (not part of evaluate()'s dict nor of METRIC_NAMES)
+    reconstruction_levels SP_RECONSTRUCTION_LEVELS "0-6"  with reconstruction only: the pyramid levels (misc.get_masks_for_inference's stage index, 0 = conv1 ..
+                                                          6 = fc8) as ranges and single levels, e.g. "0-6", "0,3,6", "0-2,6"
     lib_path              SEMPYR_LIB             (in-tree libsempyr.so)
 """
 from __future__ import annotations
@@ -95,6 +101,56 @@ def parse_metrics(text) -> tuple:
         if w not in METRIC_NAMES:
             raise ValueError("unknown metric %r (SP_METRICS: a comma-separated subset of %s)" % (w, ", ".join(METRIC_NAMES)))
     return tuple(n for n in METRIC_NAMES if n in words)
+
+
+RECONSTRUCTION_NAMES = ("psnr", "ssim", "ms_ssim")
+
+
+def parse_reconstruction(text) -> tuple:
+    """SP_RECONSTRUCTION / ModelWrapper(reconstruction=...): "ssim,psnr" -> ("psnr", "ssim") - a comma-separated subset of
+    RECONSTRUCTION_NAMES (a list or tuple of the words is taken too), returned in RECONSTRUCTION_NAMES' order; empty or None = off: ();
+    an unknown word is an error."""
+    if isinstance(text, (tuple, list)):
+        text = ",".join(text)
+    words = [w.strip() for w in (text or "").split(",") if w.strip()]
+    for w in words:
+        if w not in RECONSTRUCTION_NAMES:
+            raise ValueError("unknown reconstruction score %r (SP_RECONSTRUCTION: a comma-separated subset of %s)"
+                             % (w, ", ".join(RECONSTRUCTION_NAMES)))
+    return tuple(n for n in RECONSTRUCTION_NAMES if n in words)
+
+
+def parse_levels(text) -> tuple:
+    """SP_RECONSTRUCTION_LEVELS / ModelWrapper(reconstruction_levels=...): "0-6", "0,3,6" or a mix ("0-2,6") -> the sorted tuple of the
+    distinct levels named, each within 0..6 (misc.get_masks_for_inference's stage index); a list or tuple of integers is taken too;
+    None or empty = all seven; anything else is an error."""
+    bad = ValueError("SP_RECONSTRUCTION_LEVELS takes levels 0..6 as ranges and single levels (\"0-6\", \"0,3,6\", \"0-2,6\"), got %r" % (text,))
+    if isinstance(text, (tuple, list)):
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in text):
+            raise bad
+        levels = set(text)
+    else:
+        if text is not None and not isinstance(text, str):
+            raise bad
+        levels = set()
+        for field in ((text or "").strip() or "0-6").split(","):
+            ends = field.strip().split("-")
+            if len(ends) not in (1, 2) or not all(e.strip().isdigit() for e in ends):
+                raise bad
+            lo, hi = int(ends[0]), int(ends[-1])
+            if lo > hi:
+                raise bad
+            levels.update(range(lo, hi + 1))
+    if not levels or min(levels) < 0 or max(levels) > 6:
+        raise bad
+    return tuple(sorted(levels))
+
+
+def _checked_levels(text) -> str:
+    """The SP_RECONSTRUCTION_LEVELS string as it is ("0-6" where unset or empty), after parse_levels has accepted it."""
+    text = (text or "").strip() or "0-6"
+    parse_levels(text)
+    return text
 
 
 GAN_LOSS_NAMES = ("lsgan", "hinge", "logistic")
@@ -220,6 +276,8 @@ class Config:
     gan_loss: str = ""
     lecam: str = ""
     apa: str = ""
+    reconstruction: str = ""
+    reconstruction_levels: str = "0-6"
 
     @classmethod
     def from_env(cls) -> "Config":
@@ -240,7 +298,9 @@ class Config:
                    clip_grad_norm=parse_clip_grad_norm(os.environ.get("SP_CLIP_GRAD_NORM")),
                    metrics=",".join(parse_metrics(os.environ.get("SP_METRICS"))),
                    gan_loss=parse_gan_loss(os.environ.get("SP_GAN_LOSS")), lecam=_checked_lecam(os.environ.get("SP_LECAM")),
-                   apa=_checked_apa(os.environ.get("SP_APA")))
+                   apa=_checked_apa(os.environ.get("SP_APA")),
+                   reconstruction=",".join(parse_reconstruction(os.environ.get("SP_RECONSTRUCTION"))),
+                   reconstruction_levels=_checked_levels(os.environ.get("SP_RECONSTRUCTION_LEVELS")))
 
 
 CFG = Config.from_env()

@@ -14,7 +14,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unuse
 SRCS="conv_igemm conv_pp conv_ppw fp8 conv_wgrad conv_wgrad_rows conv_wgrad_1x1 spectral_norm linear eltwise norm resample attention losses optim inception augment apa"
 mkdir -p build
 python3 ../../tools/gen_h16.py build > /dev/null
-keep=" api.o dispatch_h16.o reduce_queue.o metrics.o"
+keep=" api.o dispatch_h16.o reduce_queue.o metrics.o reconstruction.o"
 for f in $SRCS; do keep="$keep $f.o $f.h16.o"; done
 for o in build/*.o; do
   [ -e "$o" ] || continue
@@ -36,7 +36,8 @@ for p in "${pids[@]}"; do wait $p; done
 hipcc $FLAGS -c api.cpp -o build/api.o
 if stale build/reduce_queue.o reduce_queue.hip; then hipcc $FLAGS -c reduce_queue.hip -o build/reduce_queue.o; fi     # fp32 only: one compilation
 if stale build/metrics.o metrics.hip; then hipcc $FLAGS -c metrics.hip -o build/metrics.o; fi     # fp32 only (the pair-set metrics): one compilation
+if stale build/reconstruction.o reconstruction.hip; then hipcc $FLAGS -c reconstruction.hip -o build/reconstruction.o; fi     # widens bf16 / fp16 by bit pattern, fp32 arithmetic: one compilation
 hipcc $FLAGS -c build/dispatch_h16.cpp -o build/dispatch_h16.o
-OBJS="build/api.o build/dispatch_h16.o build/reduce_queue.o build/metrics.o"; for f in $SRCS; do OBJS="$OBJS build/$f.o build/$f.h16.o"; done
+OBJS="build/api.o build/dispatch_h16.o build/reduce_queue.o build/metrics.o build/reconstruction.o"; for f in $SRCS; do OBJS="$OBJS build/$f.o build/$f.h16.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -o $OUT
 echo "built $(realpath $OUT)"

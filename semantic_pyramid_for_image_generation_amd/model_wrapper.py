@@ -43,6 +43,11 @@ of the discriminator's REAL branch is replaced by a generated one that keeps the
 whatever module D is, from one more (B,) draw of uniforms behind the augmentation's and in front of the latents); a fixed p, or one
 steered as augment_p is, by a second ops.AdaptiveAugment with its own state; the generator, the VGG-16 and the whole G step keep the true
 real images.  It needs neither ``augment`` nor this package's Discriminator.  Off by default: no draw, no launch, no allocation, no key.
+And ``reconstruction`` (or SP_RECONSTRUCTION) with ``reconstruction_levels`` (or SP_RECONSTRUCTION_LEVELS, "0-6"): per-level
+reconstruction fidelity - ``evaluate_reconstruction()`` scores every validation image against its own inversion from each level's
+features alone with PSNR, SSIM and / or MS-SSIM (reconstruction.py, csrc/reconstruction.hip), keeps the dict in
+``last_reconstruction`` and ``train()`` logs its keys where it logs the FID.  It needs no Inception weights and adds nothing to
+``evaluate()``'s dict.  Off by default: no launch, no allocation, no draw; train(), validate(), evaluate() and inference() are what they were.
 """
 from __future__ import annotations
 
@@ -86,7 +91,9 @@ class ModelWrapper(object):
                  metrics=None,
                  gan_loss=None,
                  lecam=None,
-                 apa=None) -> None:
+                 apa=None,
+                 reconstruction=None,
+                 reconstruction_levels=None) -> None:
         # nn.DataParallel wrappers are unwrapped: data parallelism is one process per GPU here
         self.generator = _unwrap(generator)
         self.discriminator = _unwrap(discriminator)
@@ -182,6 +189,20 @@ class ModelWrapper(object):
         self.last_metrics = None
         if self.metrics:
             self.logger.hyperparameter['metrics'] = ",".join(self.metrics)
+        # reconstruction: what evaluate_reconstruction() scores - a comma-separated subset of psnr, ssim, ms_ssim (reconstruction.py,
+        # DESIGN.md section 23); None: CFG.reconstruction (SP_RECONSTRUCTION); "" = off.  reconstruction_levels: the pyramid levels it
+        # inverts from ("0-6", "0,3,6", a mix, or a sequence of integers); None: CFG.reconstruction_levels.  A bad word or level is an
+        # error here.  last_reconstruction: evaluate_reconstruction()'s last dict.
+        from .config import parse_levels, parse_reconstruction
+        try:
+            self.reconstruction = parse_reconstruction(CFG.reconstruction if reconstruction is None else reconstruction)
+            self.reconstruction_levels = parse_levels(CFG.reconstruction_levels if reconstruction_levels is None else reconstruction_levels)
+        except ValueError as exc:
+            raise ops.L.SempyrError(str(exc)) from None
+        self.last_reconstruction = None
+        if self.reconstruction:
+            self.logger.hyperparameter['reconstruction'] = ",".join(self.reconstruction)
+            self.logger.hyperparameter['reconstruction_levels'] = ",".join(str(s) for s in self.reconstruction_levels)
         self._d_params = [p for p in self.discriminator.parameters()]
         self._g_params = [p for p in self.generator.parameters()]
         # clip_grad_norm: a threshold > 0 or inf; None: CFG.clip_grad_norm (SP_CLIP_GRAD_NORM - main.py's fixed keywords once more); 0 = off.
@@ -1138,6 +1159,9 @@ class ModelWrapper(object):
                         for key, value in self.last_metrics.items():
                             if key != 'fid':
                                 self.logger.log(metric_name=key, value=value)
+                    if self.reconstruction:
+                        for key, value in self.evaluate_reconstruction(device=device).items():
+                            self.logger.log(metric_name=key, value=value)
                     self.logger.log(metric_name='iterations_fid', value=self.progress_bar.n)
                     if self.path_save_metrics is not None:
                         self.logger.save_metrics(self.path_save_metrics)
@@ -1287,6 +1311,30 @@ class ModelWrapper(object):
                 self.generator.train()
         self.last_metrics = {k: float(out[k]) for k in keys}
         return dict(self.last_metrics)
+
+    @torch.no_grad()
+    def evaluate_reconstruction(self, device: str = 'cuda', use_ema=None) -> Dict[str, float]:
+        """Per-level reconstruction fidelity over the validation loader: {"psnr_level<s>", "ssim_level<s>", "ms_ssim_level<s>"} for the
+        names of ``reconstruction`` and the levels of ``reconstruction_levels`` - the float64 mean over all validation images of the score
+        of each image against the generator's output from level s of that image's own VGG-16 pyramid (reconstruction.evaluate_levels;
+        level s = inference()'s stage index, the loader's masks are ignored).  The same weight-average scope and eval / train handling as
+        evaluate(); it needs no Inception weights.  {} when the option is off or there is no validation loader.  A psnr mean over a set
+        with an identical pair is inf.  The dict is kept in ``last_reconstruction``.  `device` is accepted and ignored, as in validate()."""
+        if not self.reconstruction or self.validation_dataset_fid is None:
+            self.last_reconstruction = {}
+            return {}
+        from .reconstruction import evaluate_levels
+        dev = next(self.generator.parameters()).device
+        with self._ema_scope(use_ema):
+            self.generator.eval()
+            self.vgg16.eval()
+            try:
+                out = evaluate_levels(dataset_real=self.validation_dataset_fid, generator=self.generator, vgg16=self.vgg16, device=dev,
+                                      levels=self.reconstruction_levels, names=self.reconstruction)
+            finally:
+                self.generator.train()
+        self.last_reconstruction = {k: float(v) for k, v in out.items()}
+        return dict(self.last_reconstruction)
 
     @torch.no_grad()
     def inference(self, device: str = 'cuda', use_ema=None) -> None:

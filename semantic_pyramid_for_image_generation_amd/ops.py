@@ -2799,3 +2799,31 @@ def pairset_softmax_colsum(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
     L.call("sp_pairset_softmax_colsum", ptr(a), n, a.shape[1], ptr(w), classes, w.shape[1], ptr(bias), d, ptr(lse), ptr(h), splits,
            ptr(colsum), ptr(kl), ptr(ws), ws.numel() * ws.element_size(), stream())
     return colsum, kl
+
+
+# ---- reconstruction fidelity (csrc/reconstruction.hip): thin calls; reconstruction.py holds the scores -------------------
+def ssim_workspace_bytes(n: int, c: int, h: int, w: int, scales: int) -> int:
+    """sp_ssim_workspace (host logic: works without a GPU); SempyrError with the library's message for a shape the kernel refuses."""
+    out = ctypes.c_int64(0)
+    L.call("sp_ssim_workspace", n, c, h, w, scales, ctypes.byref(out))
+    return int(out.value)
+
+
+def ssim_stats(x: torch.Tensor, y: torch.Tensor, scales: int = 1, data_range: float = 2.0, workspace: Optional[torch.Tensor] = None):
+    """(ssim_mean, cs_mean, sqerr) of include/sempyr.h's sp_ssim_stats: float64 device tensors (n, c, scales), (n, c, scales) and (n, c).
+    x, y: (n, c, h, w) batches of one shape on one GPU, any strides, each fp32, bf16 or fp16 (read as they are: no copy, no cast).
+    workspace: a device tensor of at least ssim_workspace_bytes() bytes, 8-byte aligned (default: a fresh one); it is left holding the
+    pooled planes and partial sums in the layout the header states."""
+    with torch.no_grad():
+        x, y = x.detach(), y.detach()
+        require_gpu(x)
+        if x.dim() != 4 or tuple(y.shape) != tuple(x.shape) or y.device != x.device:
+            raise L.SempyrError("ssim_stats takes two (n, c, h, w) batches of one shape on one GPU, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        n, c, h, w = x.shape
+        ws = _pairset_ws(workspace, ssim_workspace_bytes(n, c, h, w, scales), x.device)
+        ssim_mean = torch.empty((n, c, scales), dtype=torch.float64, device=x.device)
+        cs_mean = torch.empty((n, c, scales), dtype=torch.float64, device=x.device)
+        sqerr = torch.empty((n, c), dtype=torch.float64, device=x.device)
+        L.call("sp_ssim_stats", ptr(x), sp_dtype(x.dtype), *x.stride(), ptr(y), sp_dtype(y.dtype), *y.stride(), n, c, h, w, scales,
+               float(data_range), ptr(ssim_mean), ptr(cs_mean), ptr(sqerr), ptr(ws), ws.numel() * ws.element_size(), stream())
+    return ssim_mean, cs_mean, sqerr
